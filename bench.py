@@ -2,7 +2,11 @@
 SyntheticBurstVal-shaped 14x48x48 RAW bursts -> 384x384 RGB, configs[1]: bf16, batch 8 per GPU).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--frames 14] [--size 48]
-                  [--dtype fp16|bf16|fp32] [--no-graph] [--no-cpu-baseline]
+                  [--dtype fp16|bf16|fp32] [--no-graph] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, runs W untimed steps, times K steps, writes the last step's outputs if --dump-outputs is
+given, and prints the result line.  --full adds what takes runs of its own: the per-op device timings behind the
+roofline entries (and --kernel-breakdown) and the CPU baseline; without it those entries are null.
 
 One process per GPU.  Under torchrun (WORLD_SIZE set) this process is one rank; with --gpus N > 1 and no
 WORLD_SIZE, bench.py itself starts the N ranks (torch.distributed.run, before anything touches the GPU)
@@ -59,6 +63,7 @@ KERNEL_DESC = {'conv3x3_ws': 'conv3x3_ws_kernel (persistent weight-stationary im
 # PMC traffic per launch of each kernel family, from the committed rocprofv3 --pmc passes of this same
 # command (tools/profile.sh -> tools/summarize_profile.py); bench.py cannot read its own counters
 TRAFFIC_FILE = os.path.join(REPO, 'profiles', 'pmc_traffic.json')
+DUMP_MAX_ELEMS = 1 << 22       # --dump-outputs: 16 MB of float32 per array
 
 
 def parse():
@@ -72,21 +77,32 @@ def parse():
     ap.add_argument('--dtype', default=None, choices=['fp16', 'bf16', 'fp32'],
                     help='storage dtype (default fp16 for --mode infer, bf16 for --mode train)')
     ap.add_argument('--no-graph', action='store_true')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the per-op timing passes (roofline entries, --kernel-breakdown) and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned as DIR/<name>.npy (float32; an output above '
+                         '%d elements as a fixed seeded sample of that many)' % DUMP_MAX_ELEMS)
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-seconds', type=float, default=15.0)
-    ap.add_argument('--kernel-breakdown', action='store_true', help='print per-op device times to stderr')
+    ap.add_argument('--kernel-breakdown', action='store_true',
+                    help='with --full: print per-op device times to stderr')
     ap.add_argument('--wgrad-algo', type=int, default=None,
                     help='diagnostic A/B: dbsr_set_wgrad_algo value (1 LDS-DMA ring, 0 register-staged)')
     ap.add_argument('--conv-algo', type=int, default=None,
                     help='diagnostic A/B: dbsr_set_conv_algo value (include/dbsr_hip.h); default: the library default')
     ap.add_argument('--no-op-timing', action='store_true',
-                    help='skip the per-op timing passes after the timed region (profiling runs: only graph replays)')
+                    help='with --full: skip the per-op timing passes after the timed region')
     ap.add_argument('--zero-flow', action='store_true', help='diagnostic: identity-flow stub instead of PWC-Net')
     ap.add_argument('--mode', default='infer', choices=['infer', 'train'],
                     help='train: configs[3] training step (defaults 128x128, batch 8 per GPU, RCCL grad all-reduce)')
     ap.add_argument('--dry-run', action='store_true',
                     help='CPU check of the rank launcher: gloo, no GPU; rank 0 prints every rank\'s batch shard')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps is the number of timed steps: at least 1')
+    if args.kernel_breakdown and not args.full:
+        ap.error('--kernel-breakdown prints the per-op timings, which only a --full run takes')
+    return args
 
 
 def _free_port():
@@ -122,6 +138,21 @@ def load_traffic():
         return json.load(open(TRAFFIC_FILE))
     except (OSError, ValueError):
         return {}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each named device tensor as path/<name>.npy in float32, in its own shape.  A tensor above
+    DUMP_MAX_ELEMS elements is written as the 1-D array of its values at DUMP_MAX_ELEMS flat indices (C order,
+    ascending) drawn once from a generator seeded with 0: the same indices in every run and every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + '.npy'), t.float().cpu().numpy())
 
 
 def dry_run(args, world, rank):
@@ -168,10 +199,13 @@ def train_main(args, world, rank, dev, dist):
     if dist:
         from dbsr_amd.parallel import max_over_ranks
         el = max_over_ranks(el, device=dev)
-    # per-op device times of the step (HIP events, every op re-launched back to back, outside the timed region;
-    # --no-op-timing: profiling runs, the step's own replays only)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'loss': loss})
+    # --full: per-op device times of the step (HIP events, every op re-launched back to back, outside the timed
+    # region)
     plan = tr.plans[(B, N, S, S)]
-    times = None if args.no_op_timing else plan.time_ops(torch.cuda.current_stream(dev).cuda_stream, reps=3)
+    op_timing = args.full and not args.no_op_timing
+    times = plan.time_ops(torch.cuda.current_stream(dev).cuda_stream, reps=3) if op_timing else None
     fam = {}
     for i, (fn, _, name, _) in enumerate(plan.ops):
         if name.startswith('sync.'):
@@ -306,21 +340,26 @@ def main():
             td.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(args.steps - 1):
             net(burst)
+        pred, aux = net(burst)      # only the last step's outputs are kept, so every step allocates as the others do
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
         if dist:
             from dbsr_amd.parallel import max_over_ranks
             el = max_over_ranks(el, device=dev)
             td.barrier()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {'pred': pred, 'offsets': aux['offsets'],
+                                             'fusion_weights': aux['fusion_weights']})
+        del pred, aux
 
-        # ---- per-kernel device times (HIP events), outside the timed region: inside the step as the step runs
-        # them (lanes concurrent, lane-0 convs capped while PWC-Net runs), and each op alone on the whole chip ----
+        # ---- --full: per-kernel device times (HIP events), outside the timed region: inside the step as the step
+        # runs them (lanes concurrent, lane-0 convs capped while PWC-Net runs), and each op alone on the whole chip ----
         eng = net._engine
         plan = eng.plans[(B, N, S, S)]
         times, times_chip = None, None
-        if not args.no_op_timing:
+        if args.full and not args.no_op_timing:
             cur = torch.cuda.current_stream(dev).cuda_stream
             times = plan.time_ops_in_step(cur, reps=5)
             times_chip = plan.time_ops(cur, reps=10)
@@ -429,7 +468,7 @@ def main():
                   f'{sum(t for _, t in times_chip) * 1e3:.1f} us vs step {ms_step * 1e3:.1f} us', file=sys.stderr)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(N, S, S, args.cpu_seconds)
 
     if rank == 0:

@@ -15,10 +15,15 @@ def pytest_configure(config):
 
 @pytest.fixture(scope='session')
 def golden():
-    import numpy as np
+    """golden(name): the arrays of fixture `name`, stored as tests/golden/name.npz or, above the size limit for a
+    committed file, as name.part*.npz (tests/golden/npz_parts.py)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('golden_npz_parts', os.path.join(GOLDEN, 'npz_parts.py'))
+    parts = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(parts)
 
     def load(name):
-        return dict(np.load(os.path.join(GOLDEN, name + '.npz'), allow_pickle=False))
+        return parts.load(GOLDEN, name)
     return load
 
 

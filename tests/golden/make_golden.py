@@ -156,9 +156,11 @@ def main():
         ops['pwc_flow'] = ref_net.encoder.alignment_net(src, tgt).numpy()
     out['ops'] = ops
 
+    sys.path.insert(0, HERE)
+    import npz_parts
+    tot = 0
     for name, d in out.items():
-        np.savez_compressed(os.path.join(HERE, name + '.npz'), **d)
-    tot = sum(os.path.getsize(os.path.join(HERE, n + '.npz')) for n in out)
+        tot += sum(os.path.getsize(p) for p in npz_parts.save(HERE, name, d))
     print('wrote', list(out), 'total bytes', tot)
 
 

@@ -1,4 +1,4 @@
-"""Generate tests/golden/burstsr.npz by running the REFERENCE SpatialColorAlignment
+"""Generate tests/golden/burstsr.part*.npz by running the REFERENCE SpatialColorAlignment
 (models/loss/spatial_color_alignment.py:23-108) on torch-CPU.
 
 Build container only (needs /root/reference).  Same in-process import stubs as make_golden.py (SURVEY.md
@@ -117,8 +117,9 @@ def main():
     d.update(b_ref=ref.numpy(), b_q=q.numpy(), b_test=test.numpy(), b_out=out_b.numpy(), b_valid=valid_b.numpy(),
              b_cmat=torch.stack(solutions).numpy())
     print('B: valid %.3f' % valid_b.float().mean())
-    np.savez_compressed(os.path.join(HERE, 'burstsr.npz'), **d)
-    print('wrote', os.path.join(HERE, 'burstsr.npz'), os.path.getsize(os.path.join(HERE, 'burstsr.npz')))
+    import npz_parts
+    for path in npz_parts.save(HERE, 'burstsr', d):
+        print('wrote', path, os.path.getsize(path))
 
 
 if __name__ == '__main__':

@@ -41,7 +41,8 @@ def main():
     # compute_score.py:109-111 quantisation of an unclamped prediction
     q = torch.from_numpy(pred)
     d['quantized'] = ((q.clamp(0.0, 1.0) * 2 ** 14).short().float() / (2 ** 14)).numpy()
-    np.savez_compressed(os.path.join(HERE, 'eval.npz'), **d)
+    import npz_parts
+    npz_parts.save(HERE, 'eval', d)
     print({k: (v if np.ndim(v) == 0 else v.shape) for k, v in d.items()})
 
 

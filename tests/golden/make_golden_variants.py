@@ -3,7 +3,7 @@
 Build container only (needs /root/reference; the GPU box never runs this).  Same import recipe as make_golden.py
 (cupy / lpips / admin.local stubs, the oracle's correlation for the reference's CUDA-only FunctionCorrelation, PWC-Net
 with load_pretrained=False, weights from dbsr_amd.weights.generate_state_dict(seed=0)).  Writes
-tests/golden/variants.npz:
+tests/golden/variants.part*.npz:
   merging_<case>_*   the reference WeightedSum module alone on random embeddings and offsets reaching well past
                      [-1, 1) (so offset_modulo matters), small dims
   e2e_<case>_*       the reference dbsrnet_cvpr2021 at the synthetic architecture, B=1 N=4 48x48, variant flags set
@@ -99,9 +99,9 @@ def main():
             out['e2e_offsets'] = aux['offsets'].numpy()
         print('e2e', case, 'pred mean', float(pred.mean()), 'offs absmax', float(aux['offsets'].abs().max()))
 
-    path = os.path.join(HERE, 'variants.npz')
-    np.savez_compressed(path, **out)
-    print('wrote', path, os.path.getsize(path), 'bytes')
+    import npz_parts
+    for path in npz_parts.save(HERE, 'variants', out):
+        print('wrote', path, os.path.getsize(path), 'bytes')
 
 
 if __name__ == '__main__':

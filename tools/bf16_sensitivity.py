@@ -7,7 +7,10 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, 'tests', 'golden'))
+import npz_parts                          # noqa: E402
 from oracle import dbsr_oracle as orc   # noqa: E402
 import dbsr_amd                           # noqa: E402
 from dbsr_amd import arch                 # noqa: E402
@@ -56,7 +59,7 @@ def main():
         'decoder post convs fp32': dict(fp32_layers=('decoder.predictor', 'decoder.post')),
     }
     for name in ['e2e_b1n4', 'e2e_b1n14']:
-        g = dict(np.load(f'tests/golden/{name}.npz'))
+        g = npz_parts.load(os.path.join(REPO, 'tests', 'golden'), name)
         burst = torch.from_numpy(g['burst'])
         gt = torch.from_numpy(g['gt_u16'].astype(np.float32)) / 65535
         ref = float(g['ref_psnr'][0])

@@ -12,7 +12,7 @@ if [ -n "$kexpr" ]; then
   tail -1 $out/pytest.log
 fi
 for a in "$@"; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline --kernel-breakdown --conv-algo $a > $out/bench_a$a.json 2> $out/bench_a$a.err || { echo "bench algo $a failed"; tail -20 $out/bench_a$a.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --kernel-breakdown --conv-algo $a > $out/bench_a$a.json 2> $out/bench_a$a.err || { echo "bench algo $a failed"; tail -20 $out/bench_a$a.err; exit 1; }
   python -c "import json;d=json.load(open('$out/bench_a$a.json'));print('algo $a', d['value'], d['ms_per_step'], d['roofline']['kernel'][:22], d['roofline']['frac'], 'chip', d['roofline_whole_chip']['kernel'][:22], d['roofline_whole_chip']['frac'])"
   grep "\[family\] conv3x3_ws" $out/bench_a$a.err
 done

@@ -18,7 +18,7 @@ if [ "${SUITE:-all}" != none ]; then
         > $out/pytest.log 2>&1 || { echo "pytest failed rc=$?"; grep -E "FAIL|Error|assert" $out/pytest.log | head -30; tail -5 $out/pytest.log; exit 1; }
     tail -1 $out/pytest.log; grep "precision vs oracle" $out/pytest.log || true
 fi
-timeout -k 10 300 python bench.py --kernel-breakdown --no-cpu-baseline ${@:2} > $out/bench.json 2> $out/bench.err || { echo bench failed; tail -20 $out/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --kernel-breakdown --no-cpu-baseline ${@:2} > $out/bench.json 2> $out/bench.err || { echo bench failed; tail -20 $out/bench.err; exit 1; }
 python -c "import json;d=json.load(open('$out/bench.json'));print('fp16', d['value'], d['ms_per_step'], {k: v['frac'] for k, v in d['roofline_families'].items()})"
 grep "^\[family\]" $out/bench.err | head -14
 echo done

@@ -8,6 +8,6 @@ mkdir -p $out
 export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 120 rocprofv3 --pmc $c --kernel-include-regex "resblock32|upsample_blur|conv_fuse" -d $out/$c -o run \
-        --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out/$c.log 2>&1 || { echo "pmc $c failed"; tail -5 $out/$c.log; exit 1; }
+        --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $out/$c.log 2>&1 || { echo "pmc $c failed"; tail -5 $out/$c.log; exit 1; }
 done
 echo done

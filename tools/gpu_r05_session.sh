@@ -20,9 +20,9 @@ DBSR_HIP_LIB=deep-rawburst-sr_amd/libdbsr_hip_noown.so timeout -k 10 300 python 
 rc=$?
 echo "two-lane bitwise without DBSR_OWN_SIMDS: rc=$rc"; tail -3 $out/pytest_noown.log
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit 1
-timeout -k 10 300 python bench.py --kernel-breakdown > $out/bench.json 2> $out/bench.err || { echo bench failed; tail -20 $out/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --kernel-breakdown > $out/bench.json 2> $out/bench.err || { echo bench failed; tail -20 $out/bench.err; exit 1; }
 python -c "import json;d=json.load(open('$out/bench.json'));print('fp16', d['value'], d['ms_per_step'], d.get('cpu_baseline'))"
 grep "^\[family\]" $out/bench.err | head -16
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/prof -o bench -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline \
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/prof -o bench -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline \
     > $out/prof.log 2>&1 || { echo "rocprof failed"; tail -5 $out/prof.log; exit 1; }
 echo done

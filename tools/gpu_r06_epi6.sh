@@ -11,8 +11,8 @@ tail -1 $out/pytest.log
 for r in 1 2; do
   for v in product epi6; do
     lib=deep-rawburst-sr_amd/libdbsr_hip.so; [ $v = epi6 ] && lib=$V
-    DBSR_HIP_LIB=$lib timeout -k 10 200 python bench.py --kernel-breakdown --no-cpu-baseline > $out/f_${v}_$r.json 2> $out/f_${v}_$r.err || { echo "$v fwd failed"; exit 1; }
-    DBSR_HIP_LIB=$lib timeout -k 10 200 python bench.py --mode train --kernel-breakdown --no-cpu-baseline --steps 10 > $out/t_${v}_$r.json 2> $out/t_${v}_$r.err || { echo "$v train failed"; exit 1; }
+    DBSR_HIP_LIB=$lib timeout -k 10 200 python bench.py --full --kernel-breakdown --no-cpu-baseline > $out/f_${v}_$r.json 2> $out/f_${v}_$r.err || { echo "$v fwd failed"; exit 1; }
+    DBSR_HIP_LIB=$lib timeout -k 10 200 python bench.py --full --mode train --kernel-breakdown --no-cpu-baseline --steps 10 > $out/t_${v}_$r.json 2> $out/t_${v}_$r.err || { echo "$v train failed"; exit 1; }
     echo "$v fwd $(python -c "import json;print(json.load(open('$out/f_${v}_$r.json'))['value'])") train $(python -c "import json;print(json.load(open('$out/t_${v}_$r.json'))['ms_per_step'])") $(grep -E '^pwc.refiner0 ' $out/f_${v}_$r.err | awk '{print $3, $6}')"
   done
 done

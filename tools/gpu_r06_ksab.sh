@@ -15,6 +15,6 @@ for v in "" ks_r4; do
   DBSR_HIP_LIB=$PWD/$lib timeout -k 10 120 python -u tools/bench_conv.py --only "(104 frames)" --reps 40 --algos 2,5 >> $out/ab.txt 2>&1 || { echo "ab $v failed"; tail -5 $out/ab.txt; exit 1; }
 done
 cat $out/ab.txt
-timeout -k 10 300 python bench.py --kernel-breakdown --no-cpu-baseline > $out/bench.json 2> $out/bench.err || { echo bench failed; tail -20 $out/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --kernel-breakdown --no-cpu-baseline > $out/bench.json 2> $out/bench.err || { echo bench failed; tail -20 $out/bench.err; exit 1; }
 python -c "import json;d=json.load(open('$out/bench.json'));print('fp16', d['value'], d['ms_per_step'])"
 grep -E "merge.wp|^\[family\]" $out/bench.err | head -30

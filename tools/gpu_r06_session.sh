@@ -19,7 +19,7 @@ if [ "$mode" = full ]; then
         || { echo "suite failed rc=$?"; grep -E "FAIL|Error|assert" $out/pytest.log | head -20; tail -3 $out/pytest.log; exit 1; }
     tail -1 $out/pytest.log; grep "precision vs oracle" $out/pytest.log
 fi
-timeout -k 10 300 python bench.py --kernel-breakdown > $out/bench.json 2> $out/bench.err || { echo bench failed; tail -20 $out/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --kernel-breakdown > $out/bench.json 2> $out/bench.err || { echo bench failed; tail -20 $out/bench.err; exit 1; }
 python -c "import json;d=json.load(open('$out/bench.json'));print('fp16', d['value'], d['ms_per_step'], d['roofline']['frac'], d['conv_all']['step_frac'], d.get('cpu_baseline',{}) and d['cpu_baseline']['value'])"
 grep "^\[family\]" $out/bench.err | head -18
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/prof/trace -o run --output-format csv -- python3 bench.py --steps 10 \

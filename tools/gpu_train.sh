@@ -11,7 +11,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_train.py tests/test_gpu_par
     --timeout-method thread -k "${2:-train or ws_conv or pipe_epilogue or warp_backward or chan_sum or dgrad or wgrad}" \
     > $out/pytest.log 2>&1 || { echo "pytest failed rc=$?"; grep -E "FAIL|Error|assert" $out/pytest.log | head -30; tail -5 $out/pytest.log; exit 1; }
 tail -2 $out/pytest.log
-timeout -k 10 300 python bench.py --mode train --steps 5 --warmup 2 --kernel-breakdown > $out/bench_train.json 2> $out/bench_train.err || { echo bench train failed; tail -20 $out/bench_train.err; exit 1; }
+timeout -k 10 300 python bench.py --full --mode train --steps 5 --warmup 2 --kernel-breakdown > $out/bench_train.json 2> $out/bench_train.err || { echo bench train failed; tail -20 $out/bench_train.err; exit 1; }
 python -c "import json;d=json.load(open('$out/bench_train.json'));print('train', d['value'], d['ms_per_step'], d['step_roofline'])"
 grep "^\[family\]" $out/bench_train.err | head -20
 echo done
