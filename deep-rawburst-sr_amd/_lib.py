@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get('DBSR_HIP_LIB', os.path.join(_HERE, 'libdbsr_hip.so'))
 DBSR_F32, DBSR_BF16, DBSR_F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
 OUT_NHWC, OUT_SHUFFLE, OUT_NCHW_F32 = 0, 1, 2
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 
 class FrameMap(ctypes.Structure):
@@ -173,6 +173,11 @@ def lib():
             'dbsr_color_fit': ([c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
             'dbsr_color_apply': ([c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int,
                                   c_int, c_float, c_float, c_void_p, c_void_p, c_void_p], c_int),
+            'dbsr_aligned_l1_workspace_bytes': ([c_int, c_int, c_int], c_size_t),
+            'dbsr_aligned_l1_forward': ([c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+            'dbsr_aligned_l1_backward': ([c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, Tensor, c_void_p, c_size_t, c_void_p], c_int),
         }
         for name, (args, res) in sigs.items():
             fn = getattr(L, name)
@@ -199,7 +204,8 @@ EXPORTED = ['dbsr_abi_version', 'dbsr_last_error', 'dbsr_conv_packed_elems', 'db
             'dbsr_adam_step', 'dbsr_dgrad_weights',
             'dbsr_resize_bilinear', 'dbsr_gauss_reflect', 'dbsr_color_fit', 'dbsr_color_apply', 'dbsr_pwc_dense',
             'dbsr_pwc_dense_supported', 'dbsr_pwc_extract', 'dbsr_pwc_extract_supported',
-            'dbsr_pwc_level_prep', 'dbsr_pwc_level_prep_supported']
+            'dbsr_pwc_level_prep', 'dbsr_pwc_level_prep_supported',
+            'dbsr_aligned_l1_workspace_bytes', 'dbsr_aligned_l1_forward', 'dbsr_aligned_l1_backward']
 
 
 def check(rc, what):

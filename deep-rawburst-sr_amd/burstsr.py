@@ -15,6 +15,9 @@ least-squares fit, models/loss/spatial_color_alignment.py:23-108) and reporting 
   * `SpatialColorAlignment` / `match_colors` on the HIP path: PWC flow from the engine, warps from the
     warp kernel, resampling / smoothing / colour fit / mask from csrc/sca_ops.hip.
   * `compute_score_burstsr` (compute_score.py:96-134, PSNR column; SSIM / LPIPS are out of scope).
+  * Training use (actors/dbsr_actors.py:68-80): `SpatialColorAlignment.forward` carries autograd to the
+    prediction, `PixelWiseError('l1', boundary_ignore)` with `valid=` is the objective, `PSNR(..., valid=)`
+    the statistic; the fused step is training.DBSRRealWorldTrainer (csrc/sca_train.hip).
 
 Inputs to the HIP path must be on the device; the product path has no CPU fallback.
 """
@@ -32,6 +35,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .evaluation import PSNR, imread_unchanged, imwrite, quantize_prediction
+from .evaluation import PixelWiseError as _PixelWiseError
 
 
 # ------------------------------------------------------------------------------------- Gaussian kernel
@@ -82,21 +86,18 @@ def apply_kernel(im, ksz, kernel):
     return out
 
 
-def match_colors(im_ref, im_q, im_test, ksz, gauss_kernel, bi=5, thresh=20.0):
-    """spatial_color_alignment.py:23-67: C = argmin ||smooth(im_q) C - smooth(im_ref)|| on the crop
-    [bi:-bi] per image; returns (im_test^T C, valid) with valid the bilinear-upsampled
-    (err * 255 < thresh) mask thresholded > 0.9.  The fitted matrices stay on `match_colors.last_cmat`."""
-    _dev_check(im_ref, im_q, im_test)
+def _color_fit_mask(im_ref, im_q, im_test, test_hw, ksz, gauss_kernel, bi, thresh):
+    """The colour fit and the validity mask of match_colors (:30-61), and im_test^T C (:64-67) unless im_test is
+    None (the training objective applies C itself): (c_mat [n,3,3], valid uint8 [n,1,oh,ow], out or None)."""
     n, _, h, w = im_ref.shape
-    assert im_q.shape == im_ref.shape and im_ref.shape[1] == 3 and im_test.shape[1] == 3
+    assert im_q.shape == im_ref.shape and im_ref.shape[1] == 3
     ref_s = apply_kernel(im_ref, ksz, gauss_kernel)
     q_s = apply_kernel(im_q, ksz, gauss_kernel)
     dev = im_ref.device
     s = L.stream_ptr(dev)
     cmat = torch.empty(n, 3, 3, dtype=torch.float32, device=dev)
     L.check(L.lib().dbsr_color_fit(n, h, w, bi, ref_s.data_ptr(), q_s.data_ptr(), cmat.data_ptr(), s), 'dbsr_color_fit')
-    test = im_test.float().contiguous()
-    oh, ow = test.shape[-2:]
+    oh, ow = test_hw
     # valid is [n, h - 2bi, w - 2bi] padded back by (w_q - w_valid) // 2 = bi, then upsampled by
     # im_test.shape[-1] / valid.shape[-1] (:52-59)
     f = ow / w
@@ -104,11 +105,23 @@ def match_colors(im_ref, im_q, im_test, ksz, gauss_kernel, bi=5, thresh=20.0):
         raise ValueError('match_colors: the upsampled mask (%d x %d) * %.4g does not cover the test image %dx%d'
                          % (h, w, f, oh, ow))
     r = float(np.float32(1.0 / f))
-    out = torch.empty_like(test)
+    out = torch.empty_like(im_test) if im_test is not None else None
     valid = torch.empty(n, 1, oh, ow, dtype=torch.uint8, device=dev)
     L.check(L.lib().dbsr_color_apply(n, h, w, bi, ref_s.data_ptr(), q_s.data_ptr(), cmat.data_ptr(), float(thresh),
-                                     test.data_ptr(), oh, ow, r, r, out.data_ptr(), valid.data_ptr(), s),
+                                     im_test.data_ptr() if im_test is not None else None, oh, ow, r, r,
+                                     out.data_ptr() if out is not None else None, valid.data_ptr(), s),
             'dbsr_color_apply')
+    return cmat, valid, out
+
+
+def match_colors(im_ref, im_q, im_test, ksz, gauss_kernel, bi=5, thresh=20.0):
+    """spatial_color_alignment.py:23-67: C = argmin ||smooth(im_q) C - smooth(im_ref)|| on the crop
+    [bi:-bi] per image; returns (im_test^T C, valid) with valid the bilinear-upsampled
+    (err * 255 < thresh) mask thresholded > 0.9.  The fitted matrices stay on `match_colors.last_cmat`."""
+    _dev_check(im_ref, im_q, im_test)
+    assert im_test.shape[1] == 3
+    test = im_test.float().contiguous()
+    cmat, valid, out = _color_fit_mask(im_ref, im_q, test, test.shape[-2:], ksz, gauss_kernel, bi, thresh)
     match_colors.last_cmat = cmat
     return out, valid.bool()
 
@@ -122,18 +135,101 @@ class SpatialColorAlignment(nn.Module):
         self.sr_factor = sr_factor
         self.alignment_net = alignment_net
         self.gauss_kernel, self.ksz = get_gaussian_kernel(sd=1.5)
+        self.last_alignment = None
 
-    def forward(self, pred, gt, burst_input):
-        _dev_check(pred, gt, burst_input)
-        with torch.no_grad():
-            flow = self.alignment_net(pred / (pred.max() + 1e-6), gt / (gt.max() + 1e-6))
-        pred_warped = ops.warp(pred.float().contiguous(), flow)
+    def _flow_and_fit_inputs(self, pred, gt, burst_input):
+        """(flow pred -> gt, the x1/(2 sr_factor) ground truth, the base frame's (R, G, B) warped by the
+        downsampled flow): :88-103, everything the colour fit needs; no gradient flows through any of it."""
+        flow = self.alignment_net(pred / (pred.max() + 1e-6), gt / (gt.max() + 1e-6))
         ds_factor = 1.0 / float(2.0 * self.sr_factor)
         flow_ds = resize_bilinear(flow, ds_factor, mul=ds_factor)
         burst_0 = burst_input[:, 0, [0, 1, 3]].float().contiguous()
         burst_0_warped = ops.warp(burst_0, flow_ds)
         frame_gt_ds = resize_bilinear(gt, ds_factor)
-        return match_colors(frame_gt_ds, burst_0_warped, pred_warped, self.ksz, self.gauss_kernel)
+        return flow, frame_gt_ds, burst_0_warped
+
+    def _forward(self, pred, gt, burst_input):
+        with torch.no_grad():
+            flow, frame_gt_ds, burst_0_warped = self._flow_and_fit_inputs(pred, gt, burst_input)
+            pred_warped = ops.warp(pred.float().contiguous(), flow)
+            out, valid = match_colors(frame_gt_ds, burst_0_warped, pred_warped, self.ksz, self.gauss_kernel)
+        self.last_alignment = (flow, match_colors.last_cmat, valid)
+        return out, valid
+
+    def align(self, pred, gt, burst_input):
+        """The alignment alone, for the fused training step (training.DBSRRealWorldTrainer): (flow [B,2,H,W],
+        c_mat [B,3,3], valid uint8 [B,1,H,W]); the prediction is neither warped nor colour-matched here
+        (dbsr_aligned_l1_forward does both in its one pass).  Also kept on `last_alignment`."""
+        _dev_check(pred, gt, burst_input)
+        with torch.no_grad():
+            flow, frame_gt_ds, burst_0_warped = self._flow_and_fit_inputs(pred, gt, burst_input)
+            cmat, valid, _ = _color_fit_mask(frame_gt_ds, burst_0_warped, None, pred.shape[-2:], self.ksz,
+                                             self.gauss_kernel, 5, 20.0)
+        self.last_alignment = (flow, cmat, valid)
+        return flow, cmat, valid
+
+    def forward(self, pred, gt, burst_input):
+        """(pred_warped_m, valid).  With pred.requires_grad the result carries autograd to pred (the reference's
+        training use, actors/dbsr_actors.py:75): the flow is computed without gradient (:89-90) and the colour
+        matrix does not depend on pred, so the backward is C . g followed by the warp's transpose
+        (dbsr_aligned_l1_backward).  `last_alignment` = (flow, c_mat, valid) of the last call."""
+        _dev_check(pred, gt, burst_input)
+        if torch.is_grad_enabled() and pred.requires_grad:
+            return _SCAFunction.apply(pred, self, gt, burst_input)
+        return self._forward(pred, gt, burst_input)
+
+
+class _SCAFunction(torch.autograd.Function):
+    """SpatialColorAlignment.forward under autograd w.r.t. the prediction."""
+
+    @staticmethod
+    def forward(ctx, pred, sca, gt, burst_input):
+        out, valid = sca._forward(pred.detach(), gt, burst_input)
+        flow, cmat, _ = sca.last_alignment
+        ctx.save_for_backward(flow, cmat)
+        ctx.mark_non_differentiable(valid)
+        return out, valid
+
+    @staticmethod
+    def backward(ctx, gout, gvalid):
+        flow, cmat = ctx.saved_tensors
+        gpred, _ = ops.aligned_l1_backward(gout, flow, c_mat=cmat)
+        return gpred, None, None, None
+
+
+class _MaskedL1(torch.autograd.Function):
+    """PixelWiseError('l1', boundary_ignore)(pred, gt, valid=valid) on the HIP objective kernels (identity warp
+    and colour matrix), with autograd to pred."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, valid, bi):
+        loss2, g, _ = ops.aligned_l1_forward(pred.detach(), gt, None, None, valid, bi, 1.0)
+        ctx.save_for_backward(g, loss2)
+        return loss2[0].clone()
+
+    @staticmethod
+    def backward(ctx, gloss):
+        g, loss2 = ctx.saved_tensors
+        gpred, _ = ops.aligned_l1_backward(g, None, scale=(loss2[1:] * gloss.float()).contiguous())
+        return gpred, None, None, None
+
+
+class PixelWiseError(_PixelWiseError):
+    """models/loss/image_quality_v2.py:24-66 (same signature).  The real-world recipe's case -- metric 'l1' on
+    [B, 3, H, W] device tensors with a validity mask -- runs dbsr_aligned_l1_forward / _backward; every other
+    case is evaluation.PixelWiseError's torch arithmetic (the metrics of the scoring paths)."""
+
+    def __init__(self, metric='l1', boundary_ignore=None):
+        super().__init__(metric=metric, boundary_ignore=boundary_ignore)
+        self.metric = metric
+
+    def forward(self, pred, gt, valid=None):
+        if (self.metric == 'l1' and valid is not None and pred.is_cuda and pred.dim() == 4 and pred.shape[1] == 3
+                and gt.shape == pred.shape and valid.dim() == 4 and valid.shape[1] == 1):
+            bi = self.boundary_ignore or 0
+            if pred.shape[-2] > 2 * bi and pred.shape[-1] > 2 * bi:
+                return _MaskedL1.apply(pred, gt, valid, bi)
+        return super().forward(pred, gt, valid=valid)
 
 
 # ------------------------------------------------------------------------------------- metadata

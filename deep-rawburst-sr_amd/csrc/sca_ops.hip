@@ -123,10 +123,12 @@ __global__ __launch_bounds__(256) void color_apply_kernel(int n, int h, int w, i
     float c[9];
     for (int i = 0; i < 9; ++i) c[i] = cmat[b * 9 + i];
     const long long ohw = (long long)oh * ow, o = (long long)y * ow + x;
-    const float* T = test + b * 3 * ohw;
-    const float t0 = T[o], t1 = T[o + ohw], t2 = T[o + 2 * ohw];
-    float* O = out + b * 3 * ohw;
-    for (int j = 0; j < 3; ++j) O[o + j * ohw] = t0 * c[j] + t1 * c[3 + j] + t2 * c[6 + j];
+    if (test) {                                     // (NULL: the mask only, for the training objective)
+        const float* T = test + b * 3 * ohw;
+        const float t0 = T[o], t1 = T[o + ohw], t2 = T[o + 2 * ohw];
+        float* O = out + b * 3 * ohw;
+        for (int j = 0; j < 3; ++j) O[o + j * ohw] = t0 * c[j] + t1 * c[3 + j] + t2 * c[6 + j];
+    }
 
     const long long hw = (long long)h * w;
     const float* R = ref + b * 3 * hw;
@@ -188,7 +190,7 @@ extern "C" int dbsr_color_fit(int n, int h, int w, int bi, const float* ref, con
 extern "C" int dbsr_color_apply(int n, int h, int w, int bi, const float* ref, const float* q, const float* c_mat,
                                 float thresh, const float* test, int oh, int ow, float rh, float rw, float* out,
                                 unsigned char* valid, void* stream) {
-    DBSR_CHECK_ARG(ref && q && c_mat && test && out && valid && n > 0 && oh > 0 && ow > 0, "color_apply: bad arguments");
+    DBSR_CHECK_ARG(ref && q && c_mat && !test == !out && valid && n > 0 && oh > 0 && ow > 0, "color_apply: bad arguments");
     hipLaunchKernelGGL(color_apply_kernel, dim3(nblk((long long)n * oh * ow)), dim3(256), 0, (hipStream_t)stream, n, h,
                        w, bi, ref, q, c_mat, thresh, test, oh, ow, rh, rw, out, valid);
     DBSR_LAUNCH_CHECK();

@@ -312,3 +312,65 @@ def chan_sum(t):
     L.check(L.lib().dbsr_chan_sum(N, H * W, C, L.tensor_desc(x, ld), out.data_ptr(), 0, ws.data_ptr(), need,
                                   L.stream_ptr(t.device)), 'dbsr_chan_sum')
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# real-world fine-tuning objective (csrc/sca_train.hip; dbsr_hip.h 'real-world fine-tuning objective')
+# ---------------------------------------------------------------------------------------------------
+def _f32c(t):
+    return None if t is None else t.to(torch.float32).contiguous()
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def aligned_l1_forward(pred, gt, flow, c_mat, valid, boundary_ignore, weight=1.0):
+    """dbsr_aligned_l1_forward on fp32 NCHW device tensors: returns (loss2 [2] = {loss, gradient scale}, g_pw
+    [B,3,H,W] the unnormalised dL/dwarp(pred), stats [B,2] = {masked squared-error sum, valid count} per image)."""
+    _need_cuda(pred, gt)
+    B, C, H, W = pred.shape
+    if C != 3 or gt.shape != pred.shape:
+        raise ValueError('aligned_l1: pred and gt must be [B, 3, H, W]')
+    dev = pred.device
+    pred, gt, flow, c_mat = _f32c(pred), _f32c(gt), _f32c(flow), _f32c(c_mat)
+    v8 = None if valid is None else valid.to(torch.uint8).contiguous()
+    need = L.lib().dbsr_aligned_l1_workspace_bytes(B, H, W)
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    g_pw = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
+    loss2 = torch.empty(2, dtype=torch.float32, device=dev)
+    stats = torch.empty(B, 2, dtype=torch.float32, device=dev)
+    L.check(L.lib().dbsr_aligned_l1_forward(B, H, W, int(boundary_ignore), pred.data_ptr(), _ptr(flow), _ptr(c_mat),
+                                            _ptr(v8), gt.data_ptr(), float(weight), g_pw.data_ptr(),
+                                            loss2.data_ptr(), stats.data_ptr(), ws.data_ptr(), need,
+                                            L.stream_ptr(dev)), 'dbsr_aligned_l1_forward')
+    return loss2, g_pw, stats
+
+
+def aligned_l1_backward(g_pw, flow, pred=None, c_mat=None, scale=None, want_gpred=True, dpre_dtype=None):
+    """dbsr_aligned_l1_backward: dpred = scale * warp^T(c_mat g_pw) (scale: a 1-element device tensor or None;
+    c_mat None: g_pw as it is).  Returns (gpred fp32 [B,3,H,W] or None, dpre [B,H,W,8] of dpre_dtype = the
+    ReLU-gated NHWC copy for the predictor's backward, or None)."""
+    _need_cuda(g_pw)
+    B, _, H, W = g_pw.shape
+    dev = g_pw.device
+    g_pw, flow, c_mat, pred = _f32c(g_pw), _f32c(flow), _f32c(c_mat), _f32c(pred)
+    need = L.lib().dbsr_aligned_l1_workspace_bytes(B, H, W)
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    gpred = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev) if want_gpred else None
+    dpre = torch.zeros(B, H, W, 8, dtype=dpre_dtype, device=dev) if dpre_dtype is not None else None
+    L.check(L.lib().dbsr_aligned_l1_backward(B, H, W, _ptr(pred), _ptr(flow), g_pw.data_ptr(), _ptr(c_mat),
+                                             _ptr(scale), _ptr(gpred),
+                                             L.tensor_desc(dpre, 8) if dpre is not None else L.NULL_TENSOR,
+                                             ws.data_ptr(), need, L.stream_ptr(dev)), 'dbsr_aligned_l1_backward')
+    return gpred, dpre
+
+
+def aligned_l1(pred, gt, flow, c_mat, valid, boundary_ignore, weight=1.0):
+    """The aligned L1 objective of the real-world recipe (actors/dbsr_actors.py:68-80) and its gradient:
+    loss = weight * sum(valid |warp(pred, flow)^T c_mat - gt|) / (3 sum(valid) + 1e-12) over the
+    boundary_ignore crop (flow [B,2,H,W] px, c_mat [B,3,3], valid [B,1,H,W]; each may be None).  Returns
+    (loss [1], dpred [B,3,H,W]) as device tensors; nothing is read back."""
+    loss2, g_pw, _ = aligned_l1_forward(pred, gt, flow, c_mat, valid, boundary_ignore, weight)
+    gpred, _ = aligned_l1_backward(g_pw, flow, scale=loss2[1:])
+    return loss2[:1], gpred

@@ -487,6 +487,7 @@ class DBSRTrainer:
         plan.bufs = bufs
         plan.buckets = buckets
         plan.FW, plan.gen = FW, 0
+        plan.dP = dP                    # the ReLU-gated NHWC dL/dpred the backward ops consume (objective hooks)
         plan.graphs, plan.eager_runs = None, 0      # HIP graphs of the step's segments (DBSRTrainer.step)
         return plan
 
@@ -528,6 +529,10 @@ class DBSRTrainer:
         plan.eager_runs += 1
         for w_ in works:
             w_.wait()
+        self._optimizer_step(stream)
+        return self.loss.clone()          # (self.loss is the plan's buffer, overwritten by the next step)
+
+    def _optimizer_step(self, stream):
         self.step_count += 1
         L.check(L.lib().dbsr_adam_step(self.n_params, self.flat.data_ptr(), self.flat_grad.data_ptr(),
                                        self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.lr, self.betas[0],
@@ -537,7 +542,6 @@ class DBSRTrainer:
         eng = getattr(self.net, '_engine', None)
         if eng is not None:
             eng.weights_stale = True
-        return self.loss.clone()          # (self.loss is the plan's buffer, overwritten by the next step)
 
     def forward_backward(self, burst, frame_gt):
         """Loss and gradients only (no all-reduce, no optimizer step): for tests."""
@@ -592,6 +596,122 @@ class DBSRTrainer:
         names = {id(p): n for n, p in self.net.named_parameters()}
         return {names[id(p)]: self.flat_grad[o:o + k].view(p.shape) for p in self.params
                 for (o, k) in [self.offset[id(p)]]}
+
+
+class DBSRRealWorldTrainer(DBSRTrainer):
+    """The real-world fine-tuning step (train_settings/dbsr/default_realworld.py:65-79 with
+    actors/dbsr_actors.py:50-95): DBSRTrainer's step with the L1 objective replaced by the aligned one,
+
+        pred, _ = net(burst); out, valid = sca(pred, gt, burst); loss = loss_weight * L1(out, gt, valid=valid)
+
+    The plan is DBSRTrainer's, op for op: the forward ops[:fwd_end] run, then the alignment segment (no gradient:
+    PWC flow pred -> gt, the x1/(2 sr_factor) flow and ground truth, the warped base frame, the two smoothings,
+    dbsr_color_fit, the validity mask -- burstsr.SpatialColorAlignment.align), then dbsr_aligned_l1_forward /
+    _backward write the loss and the predictor's gated gradient dP in place of the plan's l1_loss_bwd op, then
+    ops[fwd_end + 1:], the bucketed all-reduce and Adam as DBSRTrainer.step.  The alignment and the objective
+    are fp32 whatever the network's compute dtype; nothing is read back to the host during a step.
+
+    alignment_net: a dbsr_amd PWCNet on the same device (frozen; its own fp32 engine).  After a step / a
+    forward_backward: `last_alignment` = (flow, c_mat, valid) and `last_stats` = {'loss', 'psnr'} (the actor's
+    Loss/total and Stat/psnr; reading last_stats copies a few floats to the host)."""
+
+    def __init__(self, net, alignment_net, sr_factor=4, loss_weight=10.0, boundary_ignore=40, **kwargs):
+        super().__init__(net, boundary_ignore=boundary_ignore, **kwargs)
+        from .burstsr import SpatialColorAlignment
+        if self.s != 2 * sr_factor:
+            # flow / 8 must land on the burst's grid (spatial_color_alignment.py:96-103 with the x8 RAW network)
+            raise ValueError('DBSRRealWorldTrainer: the network upsamples x%d, the alignment needs x%d (2 * sr_factor)'
+                             % (self.s, 2 * sr_factor))
+        self.sca = SpatialColorAlignment(alignment_net, sr_factor=sr_factor)
+        self.loss_weight = float(loss_weight)
+        self._loss2 = torch.zeros(2, dtype=torch.float32, device=self.dev)       # {loss, gradient scale}
+        self.loss = self._loss2[:1]
+        self.last_alignment = None
+        self._stats = None
+
+    def _objective(self, plan, stream):
+        """Alignment segment + the aligned L1 forward / backward into plan.dP."""
+        lib = L.lib()
+        pred, gt = plan.bufs['pred'], plan.bufs['gt']
+        B, _, HS, WS = pred.shape
+        rw = getattr(plan, 'rw', None)
+        if rw is None:
+            need = lib.dbsr_aligned_l1_workspace_bytes(B, HS, WS)
+            rw = plan.rw = dict(need=need, ws=torch.empty(max(need, 16), dtype=torch.uint8, device=self.dev),
+                                g_pw=torch.empty(B, 3, HS, WS, dtype=torch.float32, device=self.dev),
+                                stats=torch.zeros(B, 2, dtype=torch.float32, device=self.dev))
+        flow, cmat, valid = self.sca.align(pred, gt, plan.bufs['burst'])
+        self.last_alignment = (flow, cmat, valid)
+        L.check(lib.dbsr_aligned_l1_forward(B, HS, WS, self.bi, pred.data_ptr(), flow.data_ptr(), cmat.data_ptr(),
+                                            valid.data_ptr(), gt.data_ptr(), self.loss_weight, rw['g_pw'].data_ptr(),
+                                            self._loss2.data_ptr(), rw['stats'].data_ptr(), rw['ws'].data_ptr(),
+                                            rw['need'], stream), 'dbsr_aligned_l1_forward')
+        L.check(lib.dbsr_aligned_l1_backward(B, HS, WS, pred.data_ptr(), flow.data_ptr(), rw['g_pw'].data_ptr(), None,
+                                             self._loss2.data_ptr() + 4, None, plan.dP.d(0), rw['ws'].data_ptr(),
+                                             rw['need'], stream), 'dbsr_aligned_l1_backward')
+        self._stats = rw['stats']
+
+    @property
+    def last_stats(self):
+        """{'loss': Loss/total, 'psnr': Stat/psnr} of the last step (dbsr_actors.py:82-93; PSNR(boundary_ignore)
+        with the validity mask, images with an infinite / undefined PSNR dropped, image_quality_v2.py:88-101)."""
+        if self._stats is None:
+            return None
+        st = self._stats.double().cpu()
+        psnr = [-10.0 * math.log10(sq / (3.0 * n + 1e-12)) for sq, n in st.tolist() if sq > 0.0 and n > 0.0]
+        return {'loss': float(self._loss2[0]), 'psnr': sum(psnr) / len(psnr) if psnr else 0}
+
+    def _load(self, burst, frame_gt):
+        plan = self._plan(burst.shape)
+        plan.bufs['burst'].copy_(burst.to(torch.float32), non_blocking=True)
+        plan.bufs['gt'].copy_(frame_gt.to(torch.float32), non_blocking=True)
+        return plan
+
+    def step(self, burst, frame_gt):
+        """One fine-tuning step on this rank's bursts [B,N,4,H,W] and ground truth [B,3,8H,8W]; returns the
+        rank-local loss (device tensor, shape [1])."""
+        plan = self._load(burst, frame_gt)
+        stream = L.stream_ptr(self.dev)
+        fe = plan.fwd_end
+        # the forward, [the objective, eager], then the backward cut at the gradient buckets' completion points;
+        # each segment of plan ops is one HIP graph replay after one eager step (as DBSRTrainer.step)
+        cuts = [fe + 1] + ([b[0] for b in plan.buckets] if self.world > 1 else []) + [len(plan.ops)]
+        segs = [(0, fe)] + [(a, b) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
+        if self.use_graph and plan.graphs is None and plan.eager_runs > 0:
+            plan.graphs = []
+            for a, b in segs:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    plan.run_list(plan.ops[a:b], L.stream_ptr(self.dev))
+                plan.graphs.append(g)
+        works = []
+        bi = 0
+        for si, (a, b) in enumerate(segs):
+            if plan.graphs is not None:
+                plan.graphs[si].replay()
+            else:
+                plan.run_list(plan.ops[a:b], stream)
+            if si == 0:
+                self._objective(plan, stream)
+            while bi < len(plan.buckets) and plan.buckets[bi][0] == b:
+                if self.world > 1:
+                    _, lo, hi = plan.buckets[bi]
+                    works.append(allreduce_bucket(self.flat_grad, lo, hi, self.pg))
+                bi += 1
+        plan.eager_runs += 1
+        for w_ in works:
+            w_.wait()
+        self._optimizer_step(stream)
+        return self.loss.clone()
+
+    def forward_backward(self, burst, frame_gt):
+        """Loss and gradients only (no all-reduce, no optimizer step): for tests."""
+        plan = self._load(burst, frame_gt)
+        stream = L.stream_ptr(self.dev)
+        plan.run_list(plan.ops[:plan.fwd_end], stream)
+        self._objective(plan, stream)
+        plan.run_list(plan.ops[plan.fwd_end + 1:], stream)
+        return self.loss, plan.bufs['pred']
 
 
 def trainable_convs(net):

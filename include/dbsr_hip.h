@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define DBSR_ABI_VERSION 22
+#define DBSR_ABI_VERSION 23
 
 enum { DBSR_F32 = 0, DBSR_BF16 = 1, DBSR_F16 = 2 };
 enum { DBSR_ACT_NONE = 0, DBSR_ACT_RELU = 1, DBSR_ACT_LRELU = 2 };      /* LeakyReLU slope 0.1 */
@@ -375,10 +375,48 @@ int dbsr_gauss_reflect(int planes, int h, int w, int ksz, const float* k_host, c
  * ||Q C - R|| over the [bi, h-bi) x [bi, w-bi) crop of the smoothed images ref (R) and q (Q). */
 int dbsr_color_fit(int n, int h, int w, int bi, const float* ref, const float* q, float* c_mat, void* stream);
 /* match_colors' transform + validity mask (spatial_color_alignment.py:45-67): out = test^T C per pixel,
- * valid (uint8) = bilinear-upsampled (err < thresh on the crop, 0 in the bi border) > 0.9. */
+ * valid (uint8) = bilinear-upsampled (err < thresh on the crop, 0 in the bi border) > 0.9.  test and out both
+ * NULL: the mask only (the training objective applies c_mat itself, dbsr_aligned_l1_forward). */
 int dbsr_color_apply(int n, int h, int w, int bi, const float* ref, const float* q, const float* c_mat, float thresh,
                      const float* test, int oh, int ow, float rh, float rw, float* out, unsigned char* valid,
                      void* stream);
+
+/* ---------------- real-world fine-tuning objective (ABI 23; actors/dbsr_actors.py:50-95) ----------------
+ * The aligned L1 objective of train_settings/dbsr/default_realworld.py:65-79 and its gradient w.r.t. the
+ * prediction.  fp32 NCHW planes: pred / gt / g_pw [B][3][H][W], flow [B][2][H][W] in pixels (warp.py:19-46:
+ * bilinear, zeros padding, align_corners=False, as dbsr_warp_bilinear), c_mat [B][3][3] (dbsr_color_fit), valid
+ * uint8 [B][1][H][W] (dbsr_color_apply).  The flow and c_mat carry no gradient (the reference computes the flow
+ * under no_grad and fits c_mat from gt and the base frame: spatial_color_alignment.py:87-108).
+ *
+ * dbsr_aligned_l1_forward: with pw = warp(pred, flow) and m_k = sum_c pw_c c_mat[c][k] (match_colors' im_test^T C),
+ * over the crop [bi, H-bi) x [bi, W-bi):
+ *   loss[0] = weight * sum(valid |m - gt|) / (3 sum(valid) + 1e-12)     (PixelWiseError with valid,
+ *   loss[1] = weight / (3 sum(valid) + 1e-12)  (the gradient's scale)    image_quality_v2.py:47-66)
+ *   g_pw[c] = valid * sum_k c_mat[c][k] sign(m_k - gt_k) inside the crop, 0 outside (unnormalised dL/dpw)
+ *   stats[b] = {sum valid (m - gt)^2, sum valid} of image b (NULL: none): PSNR(boundary_ignore)'s inputs,
+ *              psnr_b = -10 log10(stats[b][0] / (3 stats[b][1] + 1e-12)) (dbsr_actors.py:82-84)
+ * loss (2 floats) and stats (2 B floats) are device memory; nothing is read back.  The sums run in a fixed order
+ * (bitwise reproducible).  flow / c_mat / valid may each be NULL (identity warp / identity matrix / all valid);
+ * with all three NULL and weight 1 loss[0] is bitwise dbsr_l1_loss_backward's (fp32 dpre path).
+ *
+ * dbsr_aligned_l1_backward: dpred = *scale * warp^T(c_mat g_pw) (scale NULL: 1; c_mat NULL: g_pw as it is --
+ * dbsr_aligned_l1_forward's g_pw already holds c_mat's product; pass c_mat to back-propagate an upstream gradient
+ * of the colour-matched image; flow NULL: identity warp) written as
+ *   gpred: fp32 NCHW [B][3][H][W] (NULL: not written), and / or
+ *   dpre:  NHWC in the compute dtype, [pred > 0] * dpred in channels [c0, c0+3) -- what dbsr_l1_loss_backward /
+ *          dbsr_relu_grad produce for dbsr_head_backward (ptr NULL: not written; 16-bit with ld 8, c0 0: all 8
+ *          channels written, 3..7 zero).
+ * warp^T is a scatter-add with fp32 atomics into the zeroed workspace (3 planes; see DESIGN.md for the choice
+ * against the binned gather of dbsr_warp_backward_gather), so dpred is equal run to run up to fp32 summation
+ * order.  workspace: >= dbsr_aligned_l1_workspace_bytes (one size serves both calls), 16-B aligned. */
+size_t dbsr_aligned_l1_workspace_bytes(int B, int H, int W);
+int dbsr_aligned_l1_forward(int B, int H, int W, int boundary_ignore, const float* pred, const float* flow,
+                            const float* c_mat, const unsigned char* valid, const float* gt, float weight,
+                            float* g_pw, float* loss, float* stats, void* workspace, size_t workspace_bytes,
+                            void* stream);
+int dbsr_aligned_l1_backward(int B, int H, int W, const float* pred, const float* flow, const float* g_pw,
+                             const float* c_mat, const float* scale, float* gpred, dbsr_tensor dpre, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* ---------------- training step (BASELINE configs[3]; trainers/simple_trainer.py:78-81) ----------------
  * Backward of the DBSR part (PWC-Net is frozen, encoders.py:56-61).  Conv dgrad = dbsr_conv2d with the
