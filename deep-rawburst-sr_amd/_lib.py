@@ -178,6 +178,11 @@ def lib():
                                          c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
             'dbsr_aligned_l1_backward': ([c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, Tensor, c_void_p, c_size_t, c_void_p], c_int),
+            'dbsr_ssim_workspace_bytes': ([c_int, c_int, c_int, c_int, c_int], c_size_t),
+            'dbsr_ssim_forward': ([c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+            'dbsr_ssim_backward': ([c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
+                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
         }
         for name, (args, res) in sigs.items():
             fn = getattr(L, name)
@@ -205,7 +210,8 @@ EXPORTED = ['dbsr_abi_version', 'dbsr_last_error', 'dbsr_conv_packed_elems', 'db
             'dbsr_resize_bilinear', 'dbsr_gauss_reflect', 'dbsr_color_fit', 'dbsr_color_apply', 'dbsr_pwc_dense',
             'dbsr_pwc_dense_supported', 'dbsr_pwc_extract', 'dbsr_pwc_extract_supported',
             'dbsr_pwc_level_prep', 'dbsr_pwc_level_prep_supported',
-            'dbsr_aligned_l1_workspace_bytes', 'dbsr_aligned_l1_forward', 'dbsr_aligned_l1_backward']
+            'dbsr_aligned_l1_workspace_bytes', 'dbsr_aligned_l1_forward', 'dbsr_aligned_l1_backward',
+            'dbsr_ssim_workspace_bytes', 'dbsr_ssim_forward', 'dbsr_ssim_backward']
 
 
 def check(rc, what):

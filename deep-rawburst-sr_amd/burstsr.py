@@ -14,7 +14,7 @@ least-squares fit, models/loss/spatial_color_alignment.py:23-108) and reporting 
   * `BurstSRDataset` + `IndexedBurst` ordering (burstsr_dataset.py:243-291; sampler.py:99-150).
   * `SpatialColorAlignment` / `match_colors` on the HIP path: PWC flow from the engine, warps from the
     warp kernel, resampling / smoothing / colour fit / mask from csrc/sca_ops.hip.
-  * `compute_score_burstsr` (compute_score.py:96-134, PSNR column; SSIM / LPIPS are out of scope).
+  * `compute_score_burstsr` (compute_score.py:96-134, PSNR and SSIM columns; LPIPS is out of scope).
   * Training use (actors/dbsr_actors.py:68-80): `SpatialColorAlignment.forward` carries autograd to the
     prediction, `PixelWiseError('l1', boundary_ignore)` with `valid=` is the objective, `PSNR(..., valid=)`
     the statistic; the fused step is training.DBSRRealWorldTrainer (csrc/sca_train.hip).
@@ -34,7 +34,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from .evaluation import PSNR, imread_unchanged, imwrite, quantize_prediction
+from .evaluation import PSNR, SSIM, imread_unchanged, imwrite, quantize_prediction  # noqa: F401 (SSIM: re-export)
 from .evaluation import PixelWiseError as _PixelWiseError
 
 
@@ -502,12 +502,14 @@ def write_burstsr_sample(root, name, frames_raw, gt_raw, meta_samsung, meta_cano
 # ------------------------------------------------------------------------------------- harness
 
 def compute_score_burstsr(net, dataset, alignment_net, boundary_ignore=40, burst_sz=None, device='cuda'):
-    """compute_score.py:96-134 (PSNR column): per burst net(burst) -> quantise to 2^14 -> spatial + colour
-    alignment to the ground truth -> PSNR over the valid mask with boundary_ignore; mean over the set.
-    Returns {'psnr': mean, 'per_image': {burst_name: psnr}}."""
+    """compute_score.py:96-134 (PSNR and SSIM columns): per burst net(burst) -> quantise to 2^14 -> spatial +
+    colour alignment to the ground truth -> PSNR and SSIM over the valid mask with boundary_ignore; mean over the
+    set.  Returns {'psnr': mean, 'per_image': {burst_name: psnr}, 'ssim': mean, 'per_image_ssim': {burst_name:
+    ssim}} (LPIPS, the reference's third metric, is not computed)."""
     sca = SpatialColorAlignment(alignment_net, sr_factor=4)
     psnr_fn = PSNR(boundary_ignore=boundary_ignore)
-    per = {}
+    ssim_fn = SSIM(boundary_ignore=boundary_ignore, use_for_loss=False)
+    per, per_ssim = {}, {}
     for idx in range(len(dataset)):
         burst, gt, info = dataset[idx]
         burst = burst.unsqueeze(0).to(device)
@@ -519,4 +521,6 @@ def compute_score_burstsr(net, dataset, alignment_net, boundary_ignore=40, burst
             pred = quantize_prediction(pred.float())
             pred_m, valid = sca(pred, gt, burst)
         per[info['burst_name']] = float(psnr_fn(pred_m, gt, valid=valid))
-    return {'psnr': sum(per.values()) / max(1, len(per)), 'per_image': per}
+        per_ssim[info['burst_name']] = float(ssim_fn(pred_m, gt, valid=valid))
+    return {'psnr': sum(per.values()) / max(1, len(per)), 'per_image': per,
+            'ssim': sum(per_ssim.values()) / max(1, len(per_ssim)), 'per_image_ssim': per_ssim}

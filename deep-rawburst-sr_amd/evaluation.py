@@ -13,11 +13,14 @@ can score the drop-in network on the same files:
     RGGB, /2^14), gt/NNNN/im_rgb.png (3-channel, /2^14).  meta_info.pkl is NOT unpickled here (it is
     only used for sRGB visualisation, which is out of scope); meta_info carries 'burst_name' only.
   * `quantize_prediction` (compute_score.py:109-111) and `PSNR` / `PixelWiseError`
-    (models/loss/image_quality_v2.py:24-101), `compute_score` (compute_score.py:36-122, PSNR column)
-    and `save_results` (save_results.py:36-67).
+    (models/loss/image_quality_v2.py:24-101), `SSIM` (image_quality_v2.py:104-136 over
+    models/loss/msssim.py:10-74), `compute_score` (compute_score.py:36-122, PSNR and SSIM columns)
+    and `save_results` (save_results.py:36-67).  The third column, LPIPS, is absent: it needs the
+    `lpips` package's AlexNet / VGG weights and linear heads.
 
-Host-side Python only: the network forward is the HIP path; metrics run as torch ops on whatever
-device the predictions live on (they are reductions over one image, not part of the hot path).
+Host-side Python only: the network forward is the HIP path; PSNR runs as torch ops on whatever device
+the predictions live on; SSIM on device tensors runs the HIP kernels of csrc/metrics.hip (forward and
+gradient), on CPU tensors a torch restatement of the reference arithmetic.
 """
 import math
 import os
@@ -262,6 +265,93 @@ class PSNR(nn.Module):
         return 0 if not vals else sum(vals) / len(vals)
 
 
+def _ssim_window(channel, like):
+    """msssim.gaussian / create_window: 11 taps of exp(-(x-5)^2 / (2 * 1.5^2)) as float32 over their sum,
+    the float32 outer product, one copy per channel, then cast to the images' dtype."""
+    g = torch.tensor([math.exp(-(x - 5) ** 2 / float(2 * 1.5 ** 2)) for x in range(11)], dtype=torch.float32)
+    g = (g / g.sum()).unsqueeze(1)
+    w = g.mm(g.t()).float().expand(channel, 1, 11, 11).contiguous()
+    return w.to(device=like.device, dtype=like.dtype)
+
+
+def ssim_val_range(img):
+    """msssim.py:24-34: the dynamic range the reference infers when none is given (max > 128 -> 255 else 1,
+    min < -0.5 -> -1 else 0).  One host read."""
+    lo, hi = torch.aminmax(img.detach())
+    return (255 if float(hi) > 128 else 1) - (-1 if float(lo) < -0.5 else 0)
+
+
+def ssim_map(pred, gt, val_range):
+    """msssim.py:45-63 with the 11x11 window: the SSIM map [B, C, H-10, W-10] of [B, C, H, W] images, as
+    torch ops in the images' dtype (the CPU path of `SSIM`, and the oracle of the HIP kernels)."""
+    ch = pred.shape[1]
+    win = _ssim_window(ch, pred)
+    filt = lambda t: F.conv2d(t, win, padding=0, groups=ch)                              # noqa: E731
+    mu1, mu2 = filt(pred), filt(gt)
+    mu1_sq, mu2_sq, mu12 = mu1.pow(2), mu2.pow(2), mu1 * mu2
+    s11 = filt(pred * pred) - mu1_sq
+    s22 = filt(gt * gt) - mu2_sq
+    s12 = filt(pred * gt) - mu12
+    c1, c2 = (0.01 * val_range) ** 2, (0.03 * val_range) ** 2
+    return ((2 * mu12 + c1) * (2.0 * s12 + c2)) / ((mu1_sq + mu2_sq + c1) * (s11 + s22 + c2))
+
+
+class _SSIMHip(torch.autograd.Function):
+    """Masked mean SSIM on the HIP kernels (ops.ssim_forward / ssim_backward), with autograd to pred."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, valid, bi, val_range):
+        from . import ops
+        in_dtype = pred.dtype
+        pred, gt = pred.detach().float().contiguous(), gt.detach().float().contiguous()
+        valid = None if valid is None else valid.to(torch.uint8).contiguous()
+        result, _, _ = ops.ssim_forward(pred, gt, valid, bi, val_range)
+        ctx.save_for_backward(pred, gt, result, *(() if valid is None else (valid,)))
+        ctx.bi, ctx.val_range, ctx.in_dtype = bi, val_range, in_dtype
+        return result[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        from . import ops
+        pred, gt, result = ctx.saved_tensors[:3]
+        valid = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        gpred = ops.ssim_backward(pred, gt, valid, ctx.bi, ctx.val_range, scale=result[1:] * gout.float())
+        return gpred.to(ctx.in_dtype), None, None, None, None
+
+
+class SSIM(nn.Module):
+    """models/loss/image_quality_v2.py:104-136: the mean (or, with `valid`, the masked mean) of the SSIM map
+    inside the boundary crop; 1 - ssim when `use_for_loss`.  `val_range=None` applies the reference's
+    data-dependent rule to the cropped prediction (one host read); a number skips the read.  Device tensors
+    run the HIP kernels (gradient to pred); CPU tensors the torch restatement `ssim_map`."""
+
+    def __init__(self, boundary_ignore=None, use_for_loss=True, val_range=None):
+        super().__init__()
+        self.boundary_ignore = boundary_ignore
+        self.use_for_loss = use_for_loss
+        self.val_range = val_range
+
+    def forward(self, pred, gt, valid=None):
+        if pred.dim() == 3:
+            pred, gt = pred.unsqueeze(0), gt.unsqueeze(0)
+            if valid is not None and valid.dim() == 3:
+                valid = valid.unsqueeze(0)
+        bi = self.boundary_ignore or 0
+        crop = (lambda t: t[..., bi:-bi, bi:-bi]) if bi else (lambda t: t)
+        val_range = self.val_range if self.val_range is not None else ssim_val_range(crop(pred))
+        if pred.is_cuda:
+            value = _SSIMHip.apply(pred, gt, valid, bi, float(val_range))
+        else:
+            smap = ssim_map(crop(pred), crop(gt), val_range)
+            if valid is not None:
+                v = crop(valid)[..., 5:-5, 5:-5].to(smap.dtype)          # window centres (window size 11)
+                elem_ratio = smap.numel() / v.numel()
+                value = (smap * v).sum() / (v.sum() * elem_ratio + 1e-12)
+            else:
+                value = smap.mean()
+        return 1.0 - value if self.use_for_loss else value
+
+
 # ------------------------------------------------------------------------------------------ harness
 
 def _batches(dataset, batch, burst_sz):
@@ -274,12 +364,14 @@ def _batches(dataset, batch, burst_sz):
 
 
 def compute_score(net, dataset, boundary_ignore=40, burst_sz=None, device='cuda', batch=8):
-    """PSNR column of evaluation/synburst/compute_score.py:36-122 for one network: forward each
-    burst, quantise like :109-111, per-image PSNR with `boundary_ignore`, mean over the set.
+    """PSNR and SSIM columns of evaluation/synburst/compute_score.py:36-122 for one network: forward each
+    burst, quantise like :109-111, per-image PSNR and SSIM with `boundary_ignore`, mean over the set.
     Bursts go through the engine `batch` at a time (bursts are independent); scores stay per image.
-    Returns {'psnr': mean, 'per_image': {burst_name: psnr}}."""
+    Returns {'psnr': mean, 'per_image': {burst_name: psnr}, 'ssim': mean, 'per_image_ssim': {burst_name: ssim}}
+    (LPIPS, the reference's third metric, is not computed)."""
     psnr_fn = PSNR(boundary_ignore=boundary_ignore)
-    per = {}
+    ssim_fn = SSIM(boundary_ignore=boundary_ignore, use_for_loss=False)
+    per, per_ssim = {}, {}
     for bursts, gts, names in _batches(dataset, batch, burst_sz):
         with torch.no_grad():
             pred, _ = net(bursts.to(device))
@@ -287,7 +379,9 @@ def compute_score(net, dataset, boundary_ignore=40, burst_sz=None, device='cuda'
         gts = gts.to(pred.device)
         for i, name in enumerate(names):
             per[name] = float(psnr_fn(pred[i:i + 1], gts[i:i + 1]))
-    return {'psnr': sum(per.values()) / max(1, len(per)), 'per_image': per}
+            per_ssim[name] = float(ssim_fn(pred[i:i + 1], gts[i:i + 1]))
+    return {'psnr': sum(per.values()) / max(1, len(per)), 'per_image': per,
+            'ssim': sum(per_ssim.values()) / max(1, len(per_ssim)), 'per_image_ssim': per_ssim}
 
 
 def save_results(net, dataset, out_dir, burst_sz=None, device='cuda', batch=8):

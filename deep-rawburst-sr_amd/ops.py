@@ -374,3 +374,62 @@ def aligned_l1(pred, gt, flow, c_mat, valid, boundary_ignore, weight=1.0):
     loss2, g_pw, _ = aligned_l1_forward(pred, gt, flow, c_mat, valid, boundary_ignore, weight)
     gpred, _ = aligned_l1_backward(g_pw, flow, scale=loss2[1:])
     return loss2[:1], gpred
+
+
+# ---------------------------------------------------------------------------------------------------
+# image-quality metrics (csrc/metrics.hip; dbsr_hip.h 'image-quality metrics')
+# ---------------------------------------------------------------------------------------------------
+def _ssim_args(pred, gt, valid, boundary_ignore):
+    _need_cuda(pred, gt)
+    if pred.dim() != 4 or gt.shape != pred.shape:
+        raise ValueError('ssim: pred and gt must be [B, C, H, W] of one shape')
+    if pred.dtype != torch.float32 or gt.dtype != torch.float32:
+        raise ValueError('ssim: pred and gt must be float32')
+    B, _, H, W = pred.shape
+    v8 = None
+    if valid is not None:
+        if valid.numel() != B * H * W:
+            raise ValueError('ssim: valid must be [B, 1, H, W]')
+        v8 = valid.to(torch.uint8).contiguous()
+    return pred.contiguous(), gt.contiguous(), v8, int(boundary_ignore or 0)
+
+
+def ssim_forward(pred, gt, valid=None, boundary_ignore=0, val_range=1.0, want_map=False):
+    """dbsr_ssim_forward on fp32 NCHW device tensors: returns (result [2] = {masked mean SSIM, gradient scale},
+    sums [B,2] = {masked SSIM sum, valid window count} per image, map [B,C,H-2bi-10,W-2bi-10] or None)."""
+    pred, gt, v8, bi = _ssim_args(pred, gt, valid, boundary_ignore)
+    B, C, H, W = pred.shape
+    dev = pred.device
+    need = L.lib().dbsr_ssim_workspace_bytes(B, C, H, W, bi)
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    smap = torch.empty(B, C, max(H - 2 * bi - 10, 0), max(W - 2 * bi - 10, 0), dtype=torch.float32,
+                       device=dev) if want_map else None
+    sums = torch.empty(B, 2, dtype=torch.float32, device=dev)
+    result = torch.empty(2, dtype=torch.float32, device=dev)
+    L.check(L.lib().dbsr_ssim_forward(B, C, H, W, bi, pred.data_ptr(), gt.data_ptr(), _ptr(v8), float(val_range),
+                                      _ptr(smap), sums.data_ptr(), result.data_ptr(), ws.data_ptr(), need,
+                                      L.stream_ptr(dev)), 'dbsr_ssim_forward')
+    return result, sums, smap
+
+
+def ssim_backward(pred, gt, valid=None, boundary_ignore=0, val_range=1.0, scale=None):
+    """dbsr_ssim_backward: scale * d(sum valid * S)/dpred as fp32 [B,C,H,W], zero outside the crop (scale: a
+    1-element device tensor, e.g. ssim_forward's result[1:]; None: 1)."""
+    pred, gt, v8, bi = _ssim_args(pred, gt, valid, boundary_ignore)
+    B, C, H, W = pred.shape
+    dev = pred.device
+    if scale is None:
+        scale = torch.ones(1, dtype=torch.float32, device=dev)
+    scale = scale.to(torch.float32).contiguous()
+    gpred = torch.empty_like(pred)
+    L.check(L.lib().dbsr_ssim_backward(B, C, H, W, bi, pred.data_ptr(), gt.data_ptr(), _ptr(v8), float(val_range),
+                                       scale.data_ptr(), gpred.data_ptr(), None, 0, L.stream_ptr(dev)),
+            'dbsr_ssim_backward')
+    return gpred
+
+
+def ssim(pred, gt, valid=None, boundary_ignore=0, val_range=1.0):
+    """Masked mean SSIM (image_quality_v2.SSIM with use_for_loss=False) and its gradient: returns (ssim [1],
+    dssim/dpred [B,C,H,W]) as device tensors; nothing is read back."""
+    result, _, _ = ssim_forward(pred, gt, valid, boundary_ignore, val_range)
+    return result[:1], ssim_backward(pred, gt, valid, boundary_ignore, val_range, scale=result[1:])

@@ -418,6 +418,37 @@ int dbsr_aligned_l1_backward(int B, int H, int W, const float* pred, const float
                              const float* c_mat, const float* scale, float* gpred, dbsr_tensor dpre, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* ---------------- image-quality metrics (exports added under ABI 23: nothing existing changed) ----------------
+ * SSIM as the scoring scripts and image_quality_v2.SSIM compute it (models/loss/msssim.py:22-74,
+ * image_quality_v2.py:104-136) and its gradient w.r.t. pred.  fp32 NCHW planes pred / gt [B][C][H][W], C 1..4;
+ * valid uint8 [B][1][H][W] or NULL (all ones); B * C * H * W < 2^31.
+ *
+ * The crop drops boundary_ignore pixels on each side (0: none); the window is the 11-tap Gaussian, sigma 1.5, of
+ * msssim.gaussian (taps computed on the host: exp in double, stored as float, divided by their float sum), applied
+ * as a "valid" convolution, separably: Hm = H - 2 bi - 10, Wm = W - 2 bi - 10, both >= 1.  C1 = (0.01 val_range)^2,
+ * C2 = (0.03 val_range)^2.  valid is read at the window centres, [bi + 5, H - bi - 5) x [bi + 5, W - bi - 5).
+ *
+ * dbsr_ssim_forward:
+ *   map [B][C][Hm][Wm] (NULL: not written) = the unmasked SSIM map of msssim.py:45-63
+ *   sums[b]   = {sum over channels and windows of valid * S, sum over windows of valid} of image b
+ *   result[0] = sum_b sums[b][0] / (C sum_b sums[b][1] + 1e-12): the reference's masked mean.  Also used with
+ *               valid NULL, where the reference takes .mean(): the two differ by less than 1e-12 relative.
+ *   result[1] = 1 / (C sum_b sums[b][1] + 1e-12): the gradient's scale
+ *   sums (2 B floats) and result (2 floats) are device memory; nothing is read back.  Per-block partial sums go
+ *   to `workspace` and one block adds them in a fixed order: two runs are bitwise equal.  No atomics.
+ * dbsr_ssim_backward: gpred [B][C][H][W] = *scale * d(sum valid S)/dpred, zero outside the crop, every element
+ *   written.  Pass result + 1 (negated by the caller for the 1 - ssim loss) or any device float.  An
+ *   owner-computes gather that recomputes the maps per tile: no saved maps, no atomics, bitwise reproducible.
+ *   It uses no workspace (workspace may be NULL).
+ * workspace: >= dbsr_ssim_workspace_bytes (0 for sizes the calls refuse). */
+size_t dbsr_ssim_workspace_bytes(int B, int C, int H, int W, int boundary_ignore);
+int dbsr_ssim_forward(int B, int C, int H, int W, int boundary_ignore, const float* pred, const float* gt,
+                      const unsigned char* valid, float val_range, float* map, float* sums, float* result,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int dbsr_ssim_backward(int B, int C, int H, int W, int boundary_ignore, const float* pred, const float* gt,
+                       const unsigned char* valid, float val_range, const float* scale, float* gpred, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* ---------------- training step (BASELINE configs[3]; trainers/simple_trainer.py:78-81) ----------------
  * Backward of the DBSR part (PWC-Net is frozen, encoders.py:56-61).  Conv dgrad = dbsr_conv2d with the
  * weights of dbsr_dgrad_weights (W'[ci][co][ky][kx] = W[co][ci][kh-1-ky][kw-1-kx]) packed as a normal
