@@ -16,6 +16,8 @@ DBSR_F32, DBSR_BF16, DBSR_F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
 OUT_NHWC, OUT_SHUFFLE, OUT_NCHW_F32 = 0, 1, 2
 ABI_VERSION = 23
+SRC_F32_NCHW, SRC_U8_NHWC = 0, 1
+POST_GAINS, POST_CCM, POST_GAMMA, POST_SMOOTHSTEP = 1, 2, 4, 8
 
 
 class FrameMap(ctypes.Structure):
@@ -183,6 +185,11 @@ def lib():
                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
             'dbsr_ssim_backward': ([c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+            'dbsr_unprocess_rgb': ([c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
+            'dbsr_burst_synth': ([c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+            'dbsr_postprocess_rgb': ([c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+                                     c_int),
         }
         for name, (args, res) in sigs.items():
             fn = getattr(L, name)
@@ -211,7 +218,8 @@ EXPORTED = ['dbsr_abi_version', 'dbsr_last_error', 'dbsr_conv_packed_elems', 'db
             'dbsr_pwc_dense_supported', 'dbsr_pwc_extract', 'dbsr_pwc_extract_supported',
             'dbsr_pwc_level_prep', 'dbsr_pwc_level_prep_supported',
             'dbsr_aligned_l1_workspace_bytes', 'dbsr_aligned_l1_forward', 'dbsr_aligned_l1_backward',
-            'dbsr_ssim_workspace_bytes', 'dbsr_ssim_forward', 'dbsr_ssim_backward']
+            'dbsr_ssim_workspace_bytes', 'dbsr_ssim_forward', 'dbsr_ssim_backward',
+            'dbsr_unprocess_rgb', 'dbsr_burst_synth', 'dbsr_postprocess_rgb']
 
 
 def check(rc, what):

@@ -1,5 +1,6 @@
-"""Seeded synthetic bursts (the reference's cv2-based generator, data/synthetic_burst_generation.py,
-cannot run here: no cv2, no datasets).
+"""Seeded synthetic bursts for the benchmark and the tests (no image needed).  The reference's generator,
+data/synthetic_burst_generation.py, which makes the training distribution from real images, is
+dbsr_amd/synthetic.py; this module stays as it was.
 
 A smooth random RGB scene (sum of low-frequency sinusoids + mild texture) at the SR resolution is
 translated per frame by a random sub-pixel shift (frame 0 unshifted), box-downsampled by

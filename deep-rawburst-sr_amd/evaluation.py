@@ -400,3 +400,31 @@ def load_saved_prediction(path):
     """compute_score.py:102-104: a saved prediction back to [1,3,H,W] float /2^14."""
     im = imread_unchanged(path)
     return (torch.from_numpy(im.astype(np.float32)) / 2 ** 14).permute(2, 0, 1).float().unsqueeze(0)
+
+
+def save_visualization(net, dataset, out_dir, burst_sz=None, device='cuda', save_gt=False):
+    """evaluation/synburst/visualize_results.py's image: each prediction turned into a viewable 8-bit sRGB PNG by
+    synthetic.SimplePostProcess (the inverse camera pipeline, on the HIP kernel) and written with `png_write`
+    (RGB order).  `dataset[i]` must be (burst [N,4,H,W], gt, meta_info) with the generator's meta_info keys
+    (cam2rgb, rgb_gain, red_gain, blue_gain, gamma, smoothstep): SyntheticBurstVal, which does not unpickle its
+    meta_info.pkl, is refused.  save_gt also writes <name>_gt.png.  Returns the written paths."""
+    from .synthetic import SimplePostProcess
+    post = SimplePostProcess(return_np=True)
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for i in range(len(dataset)):
+        burst, gt, meta = dataset[i]
+        missing = [k for k in ('cam2rgb', 'rgb_gain', 'red_gain', 'blue_gain', 'gamma', 'smoothstep') if k not in meta]
+        if missing:
+            raise ValueError('save_visualization: sample %d carries no camera meta_info (missing %s)' % (i, missing))
+        if burst_sz is not None:
+            burst = burst[:burst_sz]
+        with torch.no_grad():
+            pred, _ = net(burst.unsqueeze(0).to(device))
+        name = meta.get('burst_name', '{:04d}'.format(i))
+        path = os.path.join(out_dir, '{}.png'.format(name))
+        png_write(path, post.process(pred[0].float(), meta))
+        paths.append(path)
+        if save_gt:
+            png_write(os.path.join(out_dir, '{}_gt.png'.format(name)), post.process(gt.to(device).float(), meta))
+    return paths

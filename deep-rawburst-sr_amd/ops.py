@@ -433,3 +433,82 @@ def ssim(pred, gt, valid=None, boundary_ignore=0, val_range=1.0):
     dssim/dpred [B,C,H,W]) as device tensors; nothing is read back."""
     result, _, _ = ssim_forward(pred, gt, valid, boundary_ignore, val_range)
     return result[:1], ssim_backward(pred, gt, valid, boundary_ignore, val_range, scale=result[1:])
+
+
+# ---------------------------------------------------------------------------------------------------
+# synthetic training data (csrc/synth_ops.hip; dbsr_hip.h 'synthetic training data')
+# ---------------------------------------------------------------------------------------------------
+def _cam_params(params, B, what):
+    if params.shape != (B, 16) or params.dtype != torch.float32 or not params.is_cuda:
+        raise ValueError('%s: params must be a float32 device tensor [B, 16]' % what)
+    return params.contiguous()
+
+
+def unprocess_rgb(src, params):
+    """dbsr_unprocess_rgb: src float32 [B,3,Hc,Wc] in [0,1] or uint8 [B,Hc,Wc,3] RGB (device), params [B,16]
+    (rgb2cam, rgb / red / blue gain, smoothstep and gamma flags) -> linear sensor image float32 [B,3,Hc,Wc]."""
+    _need_cuda(src, params)
+    if src.dim() != 4:
+        raise ValueError('unprocess_rgb: src must be [B,3,Hc,Wc] float32 or [B,Hc,Wc,3] uint8')
+    if src.dtype == torch.uint8:
+        B, Hc, Wc, C = src.shape
+        fmt = L.SRC_U8_NHWC
+    elif src.dtype == torch.float32:
+        B, C, Hc, Wc = src.shape
+        fmt = L.SRC_F32_NCHW
+    else:
+        raise ValueError('unprocess_rgb: src must be float32 or uint8, not %s' % src.dtype)
+    if C != 3:
+        raise ValueError('unprocess_rgb: src must have 3 channels')
+    src, params = src.contiguous(), _cam_params(params, B, 'unprocess_rgb')
+    lin = torch.empty(B, 3, Hc, Wc, dtype=torch.float32, device=src.device)
+    L.check(L.lib().dbsr_unprocess_rgb(B, Hc, Wc, src.data_ptr(), fmt, params.data_ptr(), lin.data_ptr(),
+                                       L.stream_ptr(src.device)), 'dbsr_unprocess_rgb')
+    return lin
+
+
+def burst_synth(lin, ainv, border_crop, downsample_factor, noise_levels=None, z=None, want_rgb=True, want_flow=True):
+    """dbsr_burst_synth on the linear image lin float32 [B,3,Hc,Wc]: ainv [B,N,2,3] (transformed pixel -> source
+    position), noise_levels [B,2] and z [B,N,4,H2/2,W2/2] (both None: no noise).  Returns (burst [B,N,4,H2/2,W2/2],
+    burst_rgb [B,N,3,H2,W2] or None, flow [B,N,2,H2,W2] or None)."""
+    _need_cuda(lin, ainv)
+    if lin.dim() != 4 or lin.shape[1] != 3 or lin.dtype != torch.float32:
+        raise ValueError('burst_synth: lin must be float32 [B,3,Hc,Wc]')
+    B, _, Hc, Wc = lin.shape
+    if ainv.dim() != 4 or ainv.shape[0] != B or tuple(ainv.shape[2:]) != (2, 3):
+        raise ValueError('burst_synth: ainv must be [B,N,2,3]')
+    N = ainv.shape[1]
+    bc, f = int(border_crop or 0), int(downsample_factor)
+    dev = lin.device
+    lin, ainv = lin.contiguous(), _f32c(ainv)
+    H2, W2 = (Hc - 2 * bc) // max(f, 1), (Wc - 2 * bc) // max(f, 1)
+    if (z is None) != (noise_levels is None):
+        raise ValueError('burst_synth: z and noise_levels go together')
+    if z is not None:
+        if tuple(z.shape) != (B, N, 4, H2 // 2, W2 // 2) or tuple(noise_levels.shape) != (B, 2):
+            raise ValueError('burst_synth: z must be [B,N,4,H2/2,W2/2] and noise_levels [B,2]')
+        z, noise_levels = _f32c(z), _f32c(noise_levels)
+    shp = lambda c, h, w: (B, N, c, max(h, 0), max(w, 0))                                  # noqa: E731
+    burst = torch.empty(shp(4, H2 // 2, W2 // 2), dtype=torch.float32, device=dev)
+    rgb = torch.empty(shp(3, H2, W2), dtype=torch.float32, device=dev) if want_rgb else None
+    flow = torch.empty(shp(2, H2, W2), dtype=torch.float32, device=dev) if want_flow else None
+    L.check(L.lib().dbsr_burst_synth(B, N, Hc, Wc, bc, f, lin.data_ptr(), ainv.data_ptr(), _ptr(noise_levels), _ptr(z),
+                                     burst.data_ptr(), _ptr(rgb), _ptr(flow), L.stream_ptr(dev)), 'dbsr_burst_synth')
+    return burst, rgb, flow
+
+
+def postprocess_rgb(img, params, gains=True, ccm=True, gamma=True, smoothstep=True, want_f32=True, want_u8=False):
+    """dbsr_postprocess_rgb on img float32 [B,3,H,W] with params [B,16] (cam2rgb, rgb / red / blue gain, the
+    meta smoothstep and gamma flags).  Returns (sRGB float32 [B,3,H,W] or None, uint8 [B,H,W,3] RGB or None)."""
+    _need_cuda(img, params)
+    if img.dim() != 4 or img.shape[1] != 3 or img.dtype != torch.float32:
+        raise ValueError('postprocess_rgb: img must be float32 [B,3,H,W]')
+    B, _, H, W = img.shape
+    img, params = img.contiguous(), _cam_params(params, B, 'postprocess_rgb')
+    flags = ((L.POST_GAINS if gains else 0) | (L.POST_CCM if ccm else 0) | (L.POST_GAMMA if gamma else 0) |
+             (L.POST_SMOOTHSTEP if smoothstep else 0))
+    out = torch.empty_like(img) if want_f32 else None
+    u8 = torch.empty(B, H, W, 3, dtype=torch.uint8, device=img.device) if want_u8 else None
+    L.check(L.lib().dbsr_postprocess_rgb(B, H, W, img.data_ptr(), params.data_ptr(), flags, _ptr(out), _ptr(u8),
+                                         L.stream_ptr(img.device)), 'dbsr_postprocess_rgb')
+    return out, u8

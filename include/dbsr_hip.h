@@ -449,6 +449,49 @@ int dbsr_ssim_backward(int B, int C, int H, int W, int boundary_ignore, const fl
                        const unsigned char* valid, float val_range, const float* scale, float* gpred, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---------------- synthetic training data (exports added under ABI 23: nothing existing changed) ----------------
+ * The reference's rgb2rawburst (data/synthetic_burst_generation.py:23-246 over data/camera_pipeline.py) and its
+ * inverse for viewing, process_linear_image_rgb (data/postprocessing_functions.py:32-50).  fp32, stream-ordered,
+ * no host synchronisation, no allocation; per-image parameters are device memory.
+ *
+ * params [B][16] floats per image: the 3x3 colour matrix row-major (rgb2cam for unprocess, cam2rgb for
+ * postprocess), rgb_gain, red_gain, blue_gain, smoothstep flag, gamma flag (non-zero: on), 2 spare.
+ *
+ * dbsr_unprocess_rgb (rgb2rawburst:60-77): per pixel, invert_smoothstep (clamp to [0,1], 0.5 - sin(asin(1 - 2x) / 3))
+ *   if flagged, gamma_expansion (max(x, 1e-8)^2.2) if flagged, apply_ccm, safe_invert_gains (gray = channel mean,
+ *   inflection 0.9, gains (1/red, 1, 1/blue) / rgb, max(mask + (1 - mask) g, g)), clamp to [0,1].
+ *   src: DBSR_SRC_F32_NCHW fp32 [B][3][Hc][Wc] in [0,1], or DBSR_SRC_U8_NHWC uint8 [B][Hc][Wc][3] RGB (value / 255).
+ *   lin: fp32 [B][3][Hc][Wc].
+ *
+ * dbsr_burst_synth (single2lrburst, mosaic, add_noise): bil(P, q) samples plane P bilinearly at q = (x, y), taps
+ *   outside the plane contributing 0; T_f = {f/2 - 1, f/2} for even f, {(f - 1)/2} for odd f (the source pixels a
+ *   bilinear resize by 1/f reads); H2 = (Hc - 2 bc) / f, W2 = (Wc - 2 bc) / f, both even:
+ *     rgb[b,n,c,Y,X]   = mean over (i,j) in T_f x T_f of bil(lin[b,c], ainv[b,n] (bc + f X + i, bc + f Y + j, 1))
+ *     raw plane k = (R, Gr, Gb, B) <-> (c, dy, dx) = (0,0,0), (1,0,1), (1,1,0), (2,1,1)
+ *     burst[b,n,k,y,x] = clamp01(v + z sqrt(v shot + read)),  v = rgb[b,n,c_k,2y + dy_k,2x + dx_k]
+ *     flow[b,n,:,Y,X]  = ((ainv[b,n] - ainv[b,0]) (bc + f X + (f-1)/2, bc + f Y + (f-1)/2, 1)) / f
+ *   ainv [B][N][2][3]: transformed-image pixel -> source position (the inverse of the reference's t_mat).
+ *   noise_levels [B][2] (shot, read) and z [B][N][4][H2/2][W2/2] standard normals: both NULL for no noise.
+ *   burst [B][N][4][H2/2][W2/2]; burst_rgb [B][N][3][H2][W2] and flow [B][N][2][H2][W2] may be NULL (without
+ *   burst_rgb only the channel each RAW element takes is sampled; burst is bitwise the same either way).
+ *
+ * dbsr_postprocess_rgb: apply_gains ((red, 1, blue) * rgb, clamp), apply_ccm, clamp, gamma_compression
+ *   (max(x, 1e-8)^(1/2.2)) if params' flag and DBSR_POST_GAMMA, apply_smoothstep (3x^2 - 2x^3) if params' flag and
+ *   DBSR_POST_SMOOTHSTEP, clamp.  flags: DBSR_POST_* bits.  img / out_f32 fp32 [B][3][H][W]; out_u8 uint8
+ *   [B][H][W][3] RGB = (uint8)(v * 255), truncated.  Either output may be NULL, not both.
+ *
+ * Each refuses bad arguments (null required pointers, non-positive sizes, 2 bc >= min(Hc, Wc), H2 / W2 not whole
+ * or odd, f < 1, an unknown src_format) with DBSR_E_ARG before anything is launched. */
+enum { DBSR_SRC_F32_NCHW = 0, DBSR_SRC_U8_NHWC = 1 };
+enum { DBSR_POST_GAINS = 1, DBSR_POST_CCM = 2, DBSR_POST_GAMMA = 4, DBSR_POST_SMOOTHSTEP = 8 };
+int dbsr_unprocess_rgb(int B, int Hc, int Wc, const void* src, int src_format, const float* params, float* lin,
+                       void* stream);
+int dbsr_burst_synth(int B, int N, int Hc, int Wc, int bc, int f, const float* lin, const float* ainv,
+                     const float* noise_levels, const float* z, float* burst, float* burst_rgb, float* flow,
+                     void* stream);
+int dbsr_postprocess_rgb(int B, int H, int W, const float* img, const float* params, int flags, float* out_f32,
+                         unsigned char* out_u8, void* stream);
+
 /* ---------------- training step (BASELINE configs[3]; trainers/simple_trainer.py:78-81) ----------------
  * Backward of the DBSR part (PWC-Net is frozen, encoders.py:56-61).  Conv dgrad = dbsr_conv2d with the
  * weights of dbsr_dgrad_weights (W'[ci][co][ky][kx] = W[co][ci][kh-1-ky][kw-1-kx]) packed as a normal
