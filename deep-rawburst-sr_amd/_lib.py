@@ -39,6 +39,12 @@ class PwcDenseConv(ctypes.Structure):
                 ('start', ctypes.c_int), ('cout', ctypes.c_int), ('out_off', ctypes.c_int)]
 
 
+class PwcRefineConv(ctypes.Structure):
+    """dbsr_pwc_refine_conv (include/dbsr_hip.h)."""
+    _fields_ = [('w', ctypes.c_void_p), ('bias', ctypes.c_void_p), ('cin', ctypes.c_int), ('cout', ctypes.c_int),
+                ('ksize', ctypes.c_int), ('dil', ctypes.c_int)]
+
+
 class PwcExtConv(ctypes.Structure):
     """dbsr_pwc_ext_conv (include/dbsr_hip.h)."""
     _fields_ = [('w', ctypes.c_void_p), ('bias', ctypes.c_void_p), ('cin', ctypes.c_int), ('cout', ctypes.c_int),
@@ -164,6 +170,8 @@ def lib():
             'dbsr_dgrad_weights': ([c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p], c_int),
             'dbsr_pwc_dense': ([c_int, c_int, c_int, Tensor, c_int, c_void_p, Tensor, c_void_p], c_int),
             'dbsr_pwc_dense_supported': ([c_int, c_int, c_int], c_int),
+            'dbsr_pwc_refine': ([c_int, c_int, c_int, Tensor, c_void_p, Tensor, Tensor, c_void_p], c_int),
+            'dbsr_pwc_refine_supported': ([c_int, c_int, c_int], c_int),
             'dbsr_pwc_extract': ([c_int, c_int, c_int, Tensor, c_void_p, c_void_p, c_void_p], c_int),
             'dbsr_pwc_extract_supported': ([c_int, c_int], c_int),
             'dbsr_pwc_level_prep': ([c_int, c_int, c_int, c_int, c_float, Tensor, Tensor, Tensor, Tensor, c_int, Tensor,
@@ -215,8 +223,8 @@ EXPORTED = ['dbsr_abi_version', 'dbsr_last_error', 'dbsr_conv_packed_elems', 'db
             'dbsr_warp_backward_gather_workspace_bytes', 'dbsr_warp_backward_gather', 'dbsr_gate_copy',
             'dbsr_adam_step', 'dbsr_dgrad_weights',
             'dbsr_resize_bilinear', 'dbsr_gauss_reflect', 'dbsr_color_fit', 'dbsr_color_apply', 'dbsr_pwc_dense',
-            'dbsr_pwc_dense_supported', 'dbsr_pwc_extract', 'dbsr_pwc_extract_supported',
-            'dbsr_pwc_level_prep', 'dbsr_pwc_level_prep_supported',
+            'dbsr_pwc_dense_supported', 'dbsr_pwc_refine', 'dbsr_pwc_refine_supported', 'dbsr_pwc_extract',
+            'dbsr_pwc_extract_supported', 'dbsr_pwc_level_prep', 'dbsr_pwc_level_prep_supported',
             'dbsr_aligned_l1_workspace_bytes', 'dbsr_aligned_l1_forward', 'dbsr_aligned_l1_backward',
             'dbsr_ssim_workspace_bytes', 'dbsr_ssim_forward', 'dbsr_ssim_backward',
             'dbsr_unprocess_rgb', 'dbsr_burst_synth', 'dbsr_postprocess_rgb']

@@ -40,6 +40,8 @@ PWC_LEVEL_CH = {1: 16, 2: 32, 3: 64, 4: 96, 5: 128, 6: 196}
 DENSE_OUT = [128, 128, 96, 64, 32]                         # pwcnet.py:123-146
 DENSE_OFF = [320, 192, 96, 32, 0]                          # channel slice of each dense conv output
 BASE_OFF = 448                                             # = sum(DENSE_OUT)
+# refiner convs 1-6 as (cin, cout, kernel, dilation), pwcnet.py:191-203: what dbsr_pwc_refine fuses
+REFINER_TAIL = [(128, 128, 3, 2), (128, 128, 3, 4), (128, 96, 3, 8), (96, 64, 3, 16), (64, 32, 3, 1), (32, 2, 3, 1)]
 
 
 def r8(c):
@@ -528,6 +530,9 @@ class PWCPlanner:
     FUSED_DENSE = True        # 16-bit coarse levels (<= 64 pixels per pair): dbsr_pwc_dense
     FUSED_EXTRACT = True      # 16-bit 64x64 frames: the whole feature pyramid in one launch (dbsr_pwc_extract)
     FUSED_PREP = True         # 16-bit: each decoder level's ConvTs, backwarp, correlation, assembly in one launch
+    # 16-bit 16x16 level (64x64 frames): refiner convs 1-6 + the residual flow in one launch (dbsr_pwc_refine);
+    # DBSR_FUSED_REFINER=0 keeps the per-conv path for A/B runs
+    FUSED_REFINER = os.environ.get('DBSR_FUSED_REFINER', '1') != '0'
     def __init__(self, pwc_module, W):
         net = pwc_module.net
         ex = net.netExtractor
@@ -678,7 +683,10 @@ class PWCPlanner:
         chans = [128, 128, 128, 96, 64, 32]
         bufs = [NHWC(P, h, w, cpad(c), dtype, device) for c in chans]
         x, xc0, cin = D2, 0, BASE_OFF + base2
-        for i in range(6):
+        fused = PWCPlanner.FUSED_REFINER and dtype != torch.float32 and \
+            lib.dbsr_pwc_refine_supported(h, w, L.dtype_code(dtype)) and \
+            [(pc.cin, pc.cout, pc.kh, pc.dil) for pc in self.ref[1:]] == REFINER_TAIL
+        for i in range(1 if fused else 6):
             pc = self.ref[i]
             if pc.dil >= h and pc.dil >= w and pc.kh == 3:
                 # dilation >= the level size (refiner 4, d 16, on the 16x16 level of a 64x64 frame): every
@@ -686,8 +694,21 @@ class PWCPlanner:
                 pc = self.ref_center(i)
             plan.conv(f'pwc.refiner{i}', pc, P, x, xc0, (h, w), bufs[i], 0, L.ACT_LRELU, cin=cin)
             x, xc0, cin = bufs[i], 0, chans[i]
-        plan.conv('pwc.refiner6', self.ref[6], P, x, 0, (h, w), None, 0, L.ACT_NONE, y_desc=flow_out.d(0),
-                  res=fl2)
+        if fused:
+            # refiner convs 1-6 + the residual flow in one launch, activations in LDS (csrc/pwc_refine.hip)
+            pcs = [self.ref_center(i) if i == 4 else self.ref[i] for i in range(1, 7)]
+            convs = (L.PwcRefineConv * 6)(*[
+                L.PwcRefineConv(pc.w.data_ptr(), pc.bias.data_ptr() if pc.bias is not None else None, pc.cin, pc.cout,
+                                pc.kh, pc.dil) for pc in pcs])
+            # algorithmic FLOPs of the six convs as the per-conv path counts them (refiner 4 as its centre tap)
+            flop = sum(2.0 * P * h * w * pc.cout * pc.cin * pc.kh * pc.kw for pc in pcs)
+            plan.keep.append(convs)
+            plan.add('pwc.refiner1-6', lib.dbsr_pwc_refine, P, h, w, x.d(0), convs, fl2.d(0), flow_out.d(0),
+                     work=('flop', flop))
+            plan.kernel[len(plan.ops) - 1] = 'pwc_dense'
+        else:
+            plan.conv('pwc.refiner6', self.ref[6], P, x, 0, (h, w), None, 0, L.ACT_NONE, y_desc=flow_out.d(0),
+                      res=fl2)
         plan.keep.extend(bufs)
 
 
@@ -695,7 +716,10 @@ class PWCPlanner:
 # DBSR engine
 # ==================================================================================================
 class DBSREngine:
-    LANE0_CU_SHARE = 0.5      # CU share of lane 0's persistent convs while the PWC lane runs (tools/capbench.sh)
+    # CU share of lane 0's persistent convs while the PWC lane runs (tools/capbench.sh, tools/sweep_engine.py).  0.5
+    # until the fused refiner tail shortened the PWC lane; 0.5625 (144 of 256 CUs) leaves it 112 CUs, one per pair
+    # block of dbsr_pwc_refine at the bench shape (104 pairs)
+    LANE0_CU_SHARE = 0.5625
     # the first LANE0_EARLY_CONVS encoder convs (enc.init, enc.res0.conv1, ...) at CU share LANE0_EARLY_SHARE instead:
     # PWC-Net's coarse levels (1x1 .. 8x8 pixels per pair) leave most of the chip idle while they run
     LANE0_EARLY_CONVS = 0

@@ -335,6 +335,22 @@ int dbsr_pwc_dense(int P, int h, int w, dbsr_tensor D, int dense_ch, const dbsr_
 /* 1 if dbsr_pwc_dense has an LDS tile for an h x w level with ld channels in D (else use dbsr_conv2d). */
 int dbsr_pwc_dense_supported(int h, int w, int ld);
 
+/* Fused tail of the PWC refiner on the 16x16 level (pwcnet.py:186-207, :231): refiner convs 1-6 in one launch,
+ * one block per pair with the activations in LDS.  x: refiner conv 0's output [P][16][16][>= 128] (16-bit);
+ * convs[0..5]: 128 -> 128 d2, 128 -> 128 d4, 128 -> 96 d8, 96 -> 64 (the d16 conv's centre tap packed as a 1x1
+ * conv: every other tap reads zero padding on a 16x16 image), 64 -> 32, 32 -> 2; each LeakyReLU(0.1)(conv + bias)
+ * rounded to x's dtype, the last conv + bias + res_flow (fp32) written as fp32 to flow_out.  Weights packed by
+ * dbsr_conv_pack_weights in x's dtype.  Anything else is refused (DBSR_E_ARG) before any launch. */
+typedef struct {
+    const void* w;
+    const float* bias;
+    int cin, cout, ksize, dil;
+} dbsr_pwc_refine_conv;
+int dbsr_pwc_refine(int P, int h, int w, dbsr_tensor x, const dbsr_pwc_refine_conv* convs, dbsr_tensor res_flow,
+                    dbsr_tensor flow_out, void* stream);
+/* 1 if dbsr_pwc_refine serves an h x w level in `dtype` (16x16, DBSR_BF16 / DBSR_F16). */
+int dbsr_pwc_refine_supported(int h, int w, int dtype);
+
 /* The PWC-Net feature pyramid (Extractor.forward, pwcnet.py:103-111) of F 64x64 frames in one launch:
  * convs[3l + j] = level l+1's conv j (j = 0: 3x3 stride 2, j = 1, 2: 3x3 stride 1), channels 3 -> 16 -> 32 ->
  * 64 -> 96 -> 128 -> 196, each + bias + LeakyReLU(0.1); weights packed by dbsr_conv_pack_weights (16-bit).
