@@ -14,13 +14,14 @@ can score the drop-in network on the same files:
     only used for sRGB visualisation, which is out of scope); meta_info carries 'burst_name' only.
   * `quantize_prediction` (compute_score.py:109-111) and `PSNR` / `PixelWiseError`
     (models/loss/image_quality_v2.py:24-101), `SSIM` (image_quality_v2.py:104-136 over
-    models/loss/msssim.py:10-74), `compute_score` (compute_score.py:36-122, PSNR and SSIM columns)
-    and `save_results` (save_results.py:36-67).  The third column, LPIPS, is absent: it needs the
-    `lpips` package's AlexNet / VGG weights and linear heads.
+    models/loss/msssim.py:10-74), `MSSSIM` (msssim.py:77-103), `compute_score` (compute_score.py:36-122,
+    PSNR and SSIM columns, MS-SSIM on request) and `save_results` (save_results.py:36-67).  The last
+    column, LPIPS, is absent: it needs the `lpips` package's AlexNet / VGG weights and linear heads.
 
 Host-side Python only: the network forward is the HIP path; PSNR runs as torch ops on whatever device
 the predictions live on; SSIM on device tensors runs the HIP kernels of csrc/metrics.hip (forward and
-gradient), on CPU tensors a torch restatement of the reference arithmetic.
+gradient), on CPU tensors a torch restatement of the reference arithmetic.  MS-SSIM is host-side only: a
+torch restatement on CPU tensors.
 """
 import math
 import os
@@ -352,6 +353,115 @@ class SSIM(nn.Module):
         return 1.0 - value if self.use_for_loss else value
 
 
+# ------------------------------------------------------------------------------------------ MS-SSIM
+
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)       # msssim.py:79, held as float32
+MSSSIM_MIN_SIDE = 32                                             # the reference pools a fifth time (msssim.py:88)
+
+
+def _gauss_window(k, channel, like):
+    """msssim.gaussian(k, 1.5) / create_window: k taps of exp(-(x - k//2)^2 / (2 * 1.5^2)) as float32 over their sum
+    (off-centre for even k), the float32 outer product, one copy per channel, then cast to the images' dtype as
+    msssim.SSIM.forward does."""
+    g = torch.tensor([math.exp(-(x - k // 2) ** 2 / float(2 * 1.5 ** 2)) for x in range(k)], dtype=torch.float32)
+    g = (g / g.sum()).unsqueeze(1)
+    w = g.mm(g.t()).float().expand(channel, 1, k, k).contiguous()
+    return w.to(device=like.device, dtype=like.dtype)
+
+
+def msssim_levels(pred, gt, val_range):
+    """msssim.py:83-89 on already cropped [B, C, H, W] images: the five (s_l, cs_l) = (mean SSIM map, mean
+    contrast-structure map) over batch, channels and windows, level l + 1 being F.avg_pool2d(level l, (2, 2)) and
+    the window min(11, H_l, W_l) wide.  Torch ops in the images' dtype: what `MSSSIM` computes.  One `val_range`
+    serves all five levels (see `MSSSIM`)."""
+    if pred.dim() != 4 or min(pred.shape[-2:]) < MSSSIM_MIN_SIDE:
+        raise ValueError('msssim: the crop %s is smaller than 32 x 32 (five levels, each pooled by two)'
+                         % 'x'.join(str(v) for v in pred.shape[-2:]))
+    ch = pred.shape[1]
+    c1, c2 = (0.01 * val_range) ** 2, (0.03 * val_range) ** 2
+    out = []
+    for level in range(len(MSSSIM_WEIGHTS)):
+        if level:
+            pred, gt = F.avg_pool2d(pred, (2, 2)), F.avg_pool2d(gt, (2, 2))
+        win = _gauss_window(min(11, pred.shape[-2], pred.shape[-1]), ch, pred)
+        filt = lambda t: F.conv2d(t, win, padding=0, groups=ch)                          # noqa: E731
+        mu1, mu2 = filt(pred), filt(gt)
+        mu1_sq, mu2_sq, mu12 = mu1.pow(2), mu2.pow(2), mu1 * mu2
+        s11 = filt(pred * pred) - mu1_sq
+        s22 = filt(gt * gt) - mu2_sq
+        s12 = filt(pred * gt) - mu12
+        v1, v2 = 2.0 * s12 + c2, s11 + s22 + c2
+        cs = torch.mean(v1 / v2)
+        out.append((((2 * mu12 + c1) * v1 / ((mu1_sq + mu2_sq + c1) * v2)).mean(), cs))
+    return out
+
+
+def msssim_product(levels, normalize=False, product='reference'):
+    """msssim.py:91-103 from the five (s_l, cs_l): 'reference' is torch.prod(pow1[:-1] * pow2[-1]) as it evaluates,
+    (prod_{l<4} cs_l^w_l) * s_4^(4 w_4); 'wang2003' uses the exponent w_4 and differs in nothing else."""
+    if product not in ('reference', 'wang2003'):
+        raise ValueError("msssim: product must be 'reference' or 'wang2003', not %r" % (product,))
+    mssim, mcs = torch.stack([s for s, _ in levels]), torch.stack([c for _, c in levels])
+    weights = torch.tensor(MSSSIM_WEIGHTS, dtype=torch.float32, device=mssim.device)
+    if normalize:
+        mssim, mcs = (mssim + 1) / 2, (mcs + 1) / 2
+    pow1, pow2 = mcs ** weights, mssim ** weights
+    if product == 'reference':
+        return torch.prod(pow1[:-1] * pow2[-1])
+    return torch.prod(pow1[:-1]) * pow2[-1]
+
+
+class MSSSIM(nn.Module):
+    """models/loss/msssim.py:77-103 (`msssim.msssim`) inside the boundary crop; 1 - value when `use_for_loss`.
+
+    `product='reference'` is the reference's line 102 as it evaluates (the last level's SSIM enters four times);
+    `product='wang2003'` uses the exponent w_4 instead of 4 w_4 and differs in nothing else.  `normalize` is the
+    reference's (x + 1) / 2.  Without it a negative cs_l gives NaN, as in the reference.  `per_image` scores each
+    image as its own B = 1 call and returns [B] (the reference's size_average=False is broken for B > 1 and is not
+    offered).  There is no `valid` mask: the reference has no masked MS-SSIM and no mask survives the pooling.
+    Crops under 32 x 32 raise ValueError (the reference fails on them).
+
+    `val_range=None` applies `ssim_val_range` to the cropped prediction once (one host read) and uses that range at
+    all five levels.  The reference re-derives it per level from the pooled prediction; the two differ only if the
+    crop's max exceeds 128 while a pooled level's does not (or likewise for min and -0.5).
+
+    A host-side metric: CPU tensors run the torch restatement `msssim_levels` (differentiable by autograd); device
+    tensors raise NotImplementedError, because there is no HIP kernel for it yet and no torch fall-back on the
+    device.  `compute_score` copies each quantised prediction to the host for this column."""
+
+    def __init__(self, boundary_ignore=None, use_for_loss=False, val_range=None, normalize=False,
+                 product='reference', per_image=False):
+        super().__init__()
+        if product not in ('reference', 'wang2003'):
+            raise ValueError("msssim: product must be 'reference' or 'wang2003', not %r" % (product,))
+        self.boundary_ignore = boundary_ignore
+        self.use_for_loss = use_for_loss
+        self.val_range = val_range
+        self.normalize = normalize
+        self.product = product
+        self.per_image = per_image
+
+    def forward(self, pred, gt):
+        if pred.dim() == 3:
+            pred, gt = pred.unsqueeze(0), gt.unsqueeze(0)
+        bi = self.boundary_ignore or 0
+        crop = (lambda t: t[..., bi:-bi, bi:-bi]) if bi else (lambda t: t)
+        if min(crop(pred).shape[-2:]) < MSSSIM_MIN_SIDE:
+            raise ValueError('msssim: the crop %s is smaller than 32 x 32 (five levels, each pooled by two)'
+                             % 'x'.join(str(v) for v in crop(pred).shape[-2:]))
+        if pred.is_cuda or gt.is_cuda:
+            raise NotImplementedError('MSSSIM is a host-side metric: there is no HIP kernel for it yet and it does '
+                                      'not fall back to torch on the device; pass CPU tensors (pred.cpu())')
+        val_range = self.val_range if self.val_range is not None else ssim_val_range(crop(pred))
+        one = lambda p, g: msssim_product(msssim_levels(crop(p), crop(g), val_range), self.normalize,  # noqa: E731
+                                          self.product)
+        if self.per_image:
+            value = torch.stack([one(pred[i:i + 1], gt[i:i + 1]) for i in range(pred.shape[0])])
+        else:
+            value = one(pred, gt)
+        return 1.0 - value if self.use_for_loss else value
+
+
 # ------------------------------------------------------------------------------------------ harness
 
 def _batches(dataset, batch, burst_sz):
@@ -363,15 +473,25 @@ def _batches(dataset, batch, burst_sz):
         yield bursts, torch.stack([it[1] for it in items]), [it[2]['burst_name'] for it in items]
 
 
-def compute_score(net, dataset, boundary_ignore=40, burst_sz=None, device='cuda', batch=8):
+def compute_score(net, dataset, boundary_ignore=40, burst_sz=None, device='cuda', batch=8, metrics=('psnr', 'ssim')):
     """PSNR and SSIM columns of evaluation/synburst/compute_score.py:36-122 for one network: forward each
     burst, quantise like :109-111, per-image PSNR and SSIM with `boundary_ignore`, mean over the set.
     Bursts go through the engine `batch` at a time (bursts are independent); scores stay per image.
     Returns {'psnr': mean, 'per_image': {burst_name: psnr}, 'ssim': mean, 'per_image_ssim': {burst_name: ssim}}
-    (LPIPS, the reference's third metric, is not computed)."""
+    (LPIPS, the reference's third metric, is not computed).
+
+    `metrics` may add 'msssim', the reference's MS-SSIM column: the dict then gains 'msssim' (the mean) and
+    'per_image_msssim', computed per image on the quantised prediction with `boundary_ignore` like the other two.
+    It is opt-in because MS-SSIM refuses crops under 32 x 32, which the other columns score, and because it is
+    computed on the host (each quantised prediction is copied there; `MSSSIM` has no HIP kernel yet).  PSNR and
+    SSIM are always reported."""
+    unknown = set(metrics) - {'psnr', 'ssim', 'msssim'}
+    if unknown:
+        raise ValueError('compute_score: unknown metrics %s' % sorted(unknown))
     psnr_fn = PSNR(boundary_ignore=boundary_ignore)
     ssim_fn = SSIM(boundary_ignore=boundary_ignore, use_for_loss=False)
-    per, per_ssim = {}, {}
+    msssim_fn = MSSSIM(boundary_ignore=boundary_ignore, use_for_loss=False) if 'msssim' in metrics else None
+    per, per_ssim, per_ms = {}, {}, {}
     for bursts, gts, names in _batches(dataset, batch, burst_sz):
         with torch.no_grad():
             pred, _ = net(bursts.to(device))
@@ -380,8 +500,13 @@ def compute_score(net, dataset, boundary_ignore=40, burst_sz=None, device='cuda'
         for i, name in enumerate(names):
             per[name] = float(psnr_fn(pred[i:i + 1], gts[i:i + 1]))
             per_ssim[name] = float(ssim_fn(pred[i:i + 1], gts[i:i + 1]))
-    return {'psnr': sum(per.values()) / max(1, len(per)), 'per_image': per,
-            'ssim': sum(per_ssim.values()) / max(1, len(per_ssim)), 'per_image_ssim': per_ssim}
+            if msssim_fn is not None:
+                per_ms[name] = float(msssim_fn(pred[i:i + 1].cpu(), gts[i:i + 1].cpu()))   # host-side metric
+    res = {'psnr': sum(per.values()) / max(1, len(per)), 'per_image': per,
+           'ssim': sum(per_ssim.values()) / max(1, len(per_ssim)), 'per_image_ssim': per_ssim}
+    if msssim_fn is not None:
+        res.update(msssim=sum(per_ms.values()) / max(1, len(per_ms)), per_image_msssim=per_ms)
+    return res
 
 
 def save_results(net, dataset, out_dir, burst_sz=None, device='cuda', batch=8):
