@@ -18,6 +18,8 @@ OUT_NHWC, OUT_SHUFFLE, OUT_NCHW_F32 = 0, 1, 2
 ABI_VERSION = 23
 SRC_F32_NCHW, SRC_U8_NHWC = 0, 1
 POST_GAINS, POST_CCM, POST_GAMMA, POST_SMOOTHSTEP = 1, 2, 4, 8
+# loss-scale state buffer (dbsr_hip.h DBSR_LS_*): 32-bit word indices and the buffer's length in words
+LS_SCALE, LS_GROWTH_TRACKER, LS_FOUND_INF, LS_ADAM_STEP, LS_SKIPPED, LS_WORDS = 0, 1, 2, 3, 4, 8
 
 
 class FrameMap(ctypes.Structure):
@@ -167,6 +169,12 @@ def lib():
             'dbsr_gate_copy': ([c_int, c_int, c_int, Tensor, Tensor, Tensor, c_void_p], c_int),
             'dbsr_adam_step': ([c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int,
                                 c_float, c_void_p], c_int),
+            'dbsr_l1_loss_backward_scaled': ([c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, Tensor,
+                                              c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+            'dbsr_grad_unscale_check': ([c_ll, c_void_p, c_void_p, c_void_p], c_int),
+            'dbsr_adam_step_guarded': ([c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float,
+                                        c_float, c_float, c_void_p, c_void_p], c_int),
+            'dbsr_loss_scale_update': ([c_void_p, c_float, c_float, c_int, c_void_p], c_int),
             'dbsr_dgrad_weights': ([c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p], c_int),
             'dbsr_pwc_dense': ([c_int, c_int, c_int, Tensor, c_int, c_void_p, Tensor, c_void_p], c_int),
             'dbsr_pwc_dense_supported': ([c_int, c_int, c_int], c_int),
@@ -222,6 +230,8 @@ EXPORTED = ['dbsr_abi_version', 'dbsr_last_error', 'dbsr_conv_packed_elems', 'db
             'dbsr_fuse_backward', 'dbsr_merge_prep_backward', 'dbsr_warp_backward', 'dbsr_enc_grad_gate',
             'dbsr_warp_backward_gather_workspace_bytes', 'dbsr_warp_backward_gather', 'dbsr_gate_copy',
             'dbsr_adam_step', 'dbsr_dgrad_weights',
+            'dbsr_l1_loss_backward_scaled', 'dbsr_grad_unscale_check', 'dbsr_adam_step_guarded',
+            'dbsr_loss_scale_update',
             'dbsr_resize_bilinear', 'dbsr_gauss_reflect', 'dbsr_color_fit', 'dbsr_color_apply', 'dbsr_pwc_dense',
             'dbsr_pwc_dense_supported', 'dbsr_pwc_refine', 'dbsr_pwc_refine_supported', 'dbsr_pwc_extract',
             'dbsr_pwc_extract_supported', 'dbsr_pwc_level_prep', 'dbsr_pwc_level_prep_supported',

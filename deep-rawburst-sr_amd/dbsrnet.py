@@ -93,8 +93,9 @@ class DBSRNet(nn.Module):
     In training mode with autograd enabled (net.train(), no torch.no_grad()) the forward keeps its
     activations and `pred` carries a grad_fn: loss.backward() on any objective fills the DBSR parameters'
     .grad (PWC-Net is frozen, encoders.py:56-61) from the HIP backward kernels, and any torch.optim optimizer
-    steps them (compute dtype float32 or bfloat16).  Evaluation (net.eval() or no_grad) runs the inference
-    engine.
+    steps them (any compute dtype; with float16 scale the loss with torch.amp.GradScaler as usual: this path
+    never scales internally, DBSRTrainer's own step does).  Evaluation (net.eval() or no_grad) runs the
+    inference engine.
     """
     def __init__(self, encoder, merging, decoder):
         super().__init__()

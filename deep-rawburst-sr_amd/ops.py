@@ -512,3 +512,74 @@ def postprocess_rgb(img, params, gains=True, ccm=True, gamma=True, smoothstep=Tr
     L.check(L.lib().dbsr_postprocess_rgb(B, H, W, img.data_ptr(), params.data_ptr(), flags, _ptr(out), _ptr(u8),
                                          L.stream_ptr(img.device)), 'dbsr_postprocess_rgb')
     return out, u8
+
+
+# ---------------------------------------------------------------------------------------------------
+# dynamic loss scaling (csrc/loss_scale.hip; dbsr_hip.h 'dynamic loss scaling')
+# ---------------------------------------------------------------------------------------------------
+def loss_scale_state(scale, device):
+    """A fresh scaler state buffer (DBSR_LS_WORDS int32 words on `device`; word 0 is the fp32 scale)."""
+    st = torch.zeros(L.LS_WORDS, dtype=torch.int32, device=device)
+    st.view(torch.float32)[L.LS_SCALE] = float(scale)
+    return st
+
+
+def _ls_check(state, *ts):
+    _need_cuda(state, *ts)
+    if state.dtype != torch.int32 or state.numel() < L.LS_WORDS or not state.is_contiguous():
+        raise ValueError('loss-scale state: a contiguous int32 device tensor of %d words' % L.LS_WORDS)
+
+
+def l1_loss_backward(pred, gt, boundary_ignore, dpre_dtype=torch.float32, ld=8, state=None):
+    """dbsr_l1_loss_backward (state None) or dbsr_l1_loss_backward_scaled on fp32 NCHW device tensors: returns
+    (loss [1], dpre [B,H,W,ld] of dpre_dtype)."""
+    _need_cuda(pred, gt)
+    B, C, H, W = pred.shape
+    dev = pred.device
+    pred, gt = _f32c(pred), _f32c(gt)
+    dpre = torch.zeros(B, H, W, ld, dtype=dpre_dtype, device=dev)
+    loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    nb = (B * H * W + 255) // 256
+    ws = torch.zeros(nb, dtype=torch.float32, device=dev)
+    if state is None:
+        L.check(L.lib().dbsr_l1_loss_backward(B, C, H, W, int(boundary_ignore), pred.data_ptr(), gt.data_ptr(),
+                                              L.tensor_desc(dpre, ld), loss.data_ptr(), ws.data_ptr(), 4 * nb,
+                                              L.stream_ptr(dev)), 'dbsr_l1_loss_backward')
+    else:
+        _ls_check(state)
+        L.check(L.lib().dbsr_l1_loss_backward_scaled(B, C, H, W, int(boundary_ignore), pred.data_ptr(), gt.data_ptr(),
+                                                     state.data_ptr(), L.tensor_desc(dpre, ld), loss.data_ptr(),
+                                                     ws.data_ptr(), 4 * nb, L.stream_ptr(dev)),
+                'dbsr_l1_loss_backward_scaled')
+    return loss, dpre
+
+
+def grad_unscale_check(grad, state):
+    """dbsr_grad_unscale_check: grad (flat fp32, contiguous; any 4-B aligned view) *= 1 / state.scale in place,
+    state.found_inf set on an inf / NaN."""
+    _ls_check(state, grad)
+    if grad.dtype != torch.float32 or not grad.is_contiguous():
+        raise ValueError('grad_unscale_check: a contiguous fp32 tensor')
+    L.check(L.lib().dbsr_grad_unscale_check(grad.numel(), grad.data_ptr(), state.data_ptr(),
+                                            L.stream_ptr(grad.device)), 'dbsr_grad_unscale_check')
+    return grad
+
+
+def adam_step_guarded(param, grad, exp_avg, exp_avg_sq, state, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0):
+    """dbsr_adam_step_guarded on flat contiguous fp32 device tensors, in place."""
+    _ls_check(state, param, grad, exp_avg, exp_avg_sq)
+    for t in (param, grad, exp_avg, exp_avg_sq):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != param.numel():
+            raise ValueError('adam_step_guarded: contiguous fp32 tensors of one size')
+    L.check(L.lib().dbsr_adam_step_guarded(param.numel(), param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(),
+                                           exp_avg_sq.data_ptr(), float(lr), float(betas[0]), float(betas[1]),
+                                           float(eps), float(grad_scale), state.data_ptr(),
+                                           L.stream_ptr(param.device)), 'dbsr_adam_step_guarded')
+
+
+def loss_scale_update(state, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+    """dbsr_loss_scale_update: torch.amp.GradScaler.update on the device state."""
+    _ls_check(state)
+    L.check(L.lib().dbsr_loss_scale_update(state.data_ptr(), float(growth_factor), float(backoff_factor),
+                                           int(growth_interval), L.stream_ptr(state.device)),
+            'dbsr_loss_scale_update')

@@ -108,7 +108,9 @@ class TConv:
 class DBSRTrainer:
     """One optimisation step per call on the HIP kernels: step(burst, frame_gt) -> loss (device scalar).
 
-    net: a dbsr_amd DBSRNet on a HIP device (compute dtype bf16 or fp32).  Its DBSR parameters are
+    net: a dbsr_amd DBSRNet on a HIP device (compute dtype bf16, fp32, or fp16 with the loss scaler: `loss_scale`,
+    None / 'dynamic' / a fixed scale, with torch.amp.GradScaler's init_scale, growth_factor, backoff_factor and
+    growth_interval; its state lives on the device, loss_scale_state() reads it).  Its DBSR parameters are
     re-pointed into one flat fp32 buffer (the optimizer's master copy; the module sees the updates);
     `flat_grad` holds the step's gradients in the same layout (decoder first, then merging, then
     encoder: the order the backward completes them, so the bucketed all-reduce can start early).
@@ -121,15 +123,41 @@ class DBSRTrainer:
     FUSED_WP_OUT = True
 
     def __init__(self, net, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, boundary_ignore=40, process_group=None,
-                 bucket_bytes=4 << 20, optimizer=True):
+                 bucket_bytes=4 << 20, optimizer=True, loss_scale=None, init_scale=65536.0, growth_factor=2.0,
+                 backoff_factor=0.5, growth_interval=2000):
         dev = next(net.parameters()).device
         if dev.type != 'cuda':
             raise RuntimeError('DBSRTrainer needs the network on a HIP device')
         self.net, self.dev, self.dtype = net, dev, net.compute_dtype
-        if self.dtype == torch.float16:
-            # no loss scaling: the L1 gradient 1/count (~4.7e-8 at configs[3]) is below fp16's smallest
-            # subnormal, so an fp16 backward would underflow to zero
-            raise ValueError('DBSRTrainer: train in torch.bfloat16 or torch.float32 (fp16 has no loss scaling here)')
+        # Loss scaling (csrc/loss_scale.hip, torch.amp.GradScaler's rule on the device).  None: no scaling -- the
+        # plan and the optimizer launch are the unscaled ones -- except for an fp16 net, where it means 'dynamic':
+        # the L1 gradient 1/count (~4.7e-8 at configs[3]) is below fp16's smallest subnormal, so an unscaled
+        # fp16 backward underflows to zero.  A float is a fixed scale (no growth / backoff; steps
+        # that overflow are still skipped).  The autograd path (optimizer=False) never scales: the caller's
+        # GradScaler multiplies the loss, and the upstream gradient arrives scaled.
+        if not optimizer:
+            if loss_scale is not None:
+                raise ValueError('DBSRTrainer: optimizer=False (the autograd path) does not scale internally; scale '
+                                 'the loss with torch.amp.GradScaler')
+        elif loss_scale is None and self.dtype == torch.float16:
+            loss_scale = 'dynamic'
+        self.scaling = loss_scale is not None
+        if self.scaling:
+            dynamic = isinstance(loss_scale, str)
+            if dynamic and loss_scale != 'dynamic':
+                raise ValueError("DBSRTrainer: loss_scale is None, 'dynamic' or a positive number, got %r" % (loss_scale,))
+            scale0 = float(init_scale if dynamic else loss_scale)
+            if not (scale0 > 0.0 and math.isfinite(scale0)):
+                raise ValueError('DBSRTrainer: the loss scale must be positive and finite, got %r' % (scale0,))
+            if not (growth_factor > 0.0 and backoff_factor > 0.0 and int(growth_interval) >= 1):
+                raise ValueError('DBSRTrainer: growth_factor and backoff_factor must be > 0, growth_interval >= 1')
+            # a fixed scale is the same update with both factors 1
+            self.ls_args = (float(growth_factor), float(backoff_factor), int(growth_interval)) if dynamic \
+                else (1.0, 1.0, int(growth_interval))
+            # the scaler's state (dbsr_hip.h DBSR_LS_*): read and written by the kernels only during a step
+            self._ls = torch.zeros(L.LS_WORDS, dtype=torch.int32, device=dev)
+            self._ls.view(torch.float32)[L.LS_SCALE] = scale0
+            self._fb_inf = torch.zeros(1, dtype=torch.int32, device=dev)   # found_inf of the last forward_backward
         self.lr, self.betas, self.eps, self.bi = lr, betas, eps, boundary_ignore
         if getattr(net.encoder, 'train_alignmentnet', False):
             # the reference then backpropagates into PWC-Net (encoders.py:56-57); the HIP backward stops at the
@@ -376,8 +404,14 @@ class DBSRTrainer:
         dP = NHWC(B, HS, WS, 8, dt, dev)
         nlb = (B * HS * WS + 255) // 256
         plan.fwd_end = len(plan.ops)            # ops[:fwd_end]: the forward with saved activations (+ grad zeroing)
-        plan.add('l1_loss_bwd', lib.dbsr_l1_loss_backward, B, 3, HS, WS, self.bi, pred.data_ptr(),
-                 bufs['gt'].data_ptr(), dP.d(0), self.loss.data_ptr(), ws('l1', 4 * nlb), 4 * nlb)
+        if self.scaling:
+            # dP = scale * dL/dpre with the scale read from the scaler's state on the device (the loss stays unscaled)
+            plan.add('l1_loss_bwd', lib.dbsr_l1_loss_backward_scaled, B, 3, HS, WS, self.bi, pred.data_ptr(),
+                     bufs['gt'].data_ptr(), self._ls.data_ptr(), dP.d(0), self.loss.data_ptr(), ws('l1', 4 * nlb),
+                     4 * nlb)
+        else:
+            plan.add('l1_loss_bwd', lib.dbsr_l1_loss_backward, B, 3, HS, WS, self.bi, pred.data_ptr(),
+                     bufs['gt'].data_ptr(), dP.d(0), self.loss.data_ptr(), ws('l1', 4 * nlb), 4 * nlb)
         # autograd: the same backward from an upstream dL/dpred instead of the built-in L1 objective
         bufs['gpred'] = torch.zeros(B, 3, HS, WS, dtype=torch.float32, device=dev)
         plan.grad_in_op = (lib.dbsr_relu_grad, (B, 3, HS, WS, pred.data_ptr(), bufs['gpred'].data_ptr(), dP.d(0)),
@@ -534,7 +568,23 @@ class DBSRTrainer:
 
     def _optimizer_step(self, stream):
         self.step_count += 1
-        L.check(L.lib().dbsr_adam_step(self.n_params, self.flat.data_ptr(), self.flat_grad.data_ptr(),
+        lib = L.lib()
+        if self.scaling:
+            # Order (step() calls this after every bucket's all-reduce has completed, before anything else touches
+            # the gradients): unscale + overflow check on the SUMMED gradients, then the guarded Adam, then the
+            # scaler's update.  The all-reduce is a sum, so an inf / NaN on one rank is an inf / NaN in every
+            # rank's flat_grad: all ranks set found_inf alike and take the same skip / backoff decision from
+            # their own copy of the state, without a second collective; the states stay equal step after step.
+            # Nothing here is read back: the decision, the scale and Adam's t stay on the device.
+            L.check(lib.dbsr_grad_unscale_check(self.n_params, self.flat_grad.data_ptr(), self._ls.data_ptr(),
+                                                stream), 'grad_unscale_check')
+            L.check(lib.dbsr_adam_step_guarded(self.n_params, self.flat.data_ptr(), self.flat_grad.data_ptr(),
+                                               self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.lr,
+                                               self.betas[0], self.betas[1], self.eps, 1.0 / self.world,
+                                               self._ls.data_ptr(), stream), 'adam_step_guarded')
+            L.check(lib.dbsr_loss_scale_update(self._ls.data_ptr(), *self.ls_args, stream), 'loss_scale_update')
+        else:
+            L.check(lib.dbsr_adam_step(self.n_params, self.flat.data_ptr(), self.flat_grad.data_ptr(),
                                        self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.lr, self.betas[0],
                                        self.betas[1], self.eps, self.step_count, 1.0 / self.world, stream), 'adam')
         # the inference engine packs from the module parameters (now updated in place through their storage):
@@ -553,7 +603,38 @@ class DBSRTrainer:
         plan.bufs['burst'].copy_(burst.to(torch.float32), non_blocking=True)
         plan.bufs['gt'].copy_(frame_gt.to(torch.float32), non_blocking=True)
         plan.run(L.stream_ptr(self.dev))
+        self._unscale_only(L.stream_ptr(self.dev))
         return self.loss, plan.bufs['pred']
+
+    def _unscale_only(self, stream):
+        """forward_backward with a scaler: grads() are the true (unscaled) gradients; the overflow flag goes to
+        found_inf() and is cleared here, since no dbsr_loss_scale_update follows (the state is a step's alone)."""
+        if not self.scaling:
+            return
+        L.check(L.lib().dbsr_grad_unscale_check(self.n_params, self.flat_grad.data_ptr(), self._ls.data_ptr(),
+                                                stream), 'grad_unscale_check')
+        flag = self._ls[L.LS_FOUND_INF:L.LS_FOUND_INF + 1]
+        self._fb_inf.copy_(flag)
+        flag.zero_()
+
+    def found_inf(self):
+        """Whether the last forward_backward's gradients overflowed (copies one int to the host; for tests)."""
+        return bool(int(self._fb_inf)) if self.scaling else False
+
+    def loss_scale_state(self):
+        """{'scale', 'growth_tracker', 'steps', 'skipped'} of the loss scaler ('steps': optimizer steps applied),
+        None without one.  One small device-to-host copy: for logging and tests, never part of a step."""
+        if not self.scaling:
+            return None
+        w = self._ls.cpu()
+        return {'scale': float(w.view(torch.float32)[L.LS_SCALE]), 'growth_tracker': int(w[L.LS_GROWTH_TRACKER]),
+                'steps': int(w[L.LS_ADAM_STEP]), 'skipped': int(w[L.LS_SKIPPED])}
+
+    def set_loss_scale(self, scale):
+        """Overwrite the scaler's current scale (resuming a run; tests)."""
+        if not self.scaling:
+            raise ValueError('DBSRTrainer: built without a loss scaler')
+        self._ls.view(torch.float32)[L.LS_SCALE] = float(scale)
 
     # ---- autograd through DBSRNet.forward (the reference's own loop: pred, _ = net(burst); objective(pred,
     # gt).backward(); optimizer.step(); actors/dbsr_actors.py:27-47, trainers/simple_trainer.py:78-81) ----
@@ -616,6 +697,11 @@ class DBSRRealWorldTrainer(DBSRTrainer):
     Loss/total and Stat/psnr; reading last_stats copies a few floats to the host)."""
 
     def __init__(self, net, alignment_net, sr_factor=4, loss_weight=10.0, boundary_ignore=40, **kwargs):
+        if getattr(net, 'compute_dtype', None) == torch.float16 or kwargs.get('loss_scale') is not None:
+            # the aligned objective writes dP itself (dbsr_aligned_l1_backward, in place of the plan's l1_loss_bwd
+            # op) and is not scaled yet: refuse before anything is allocated
+            raise ValueError('DBSRRealWorldTrainer: train in torch.bfloat16 or torch.float32 (the aligned objective '
+                             'has no loss scaling here)')
         super().__init__(net, boundary_ignore=boundary_ignore, **kwargs)
         from .burstsr import SpatialColorAlignment
         if self.s != 2 * sr_factor:

@@ -590,6 +590,42 @@ int dbsr_gate_copy(int n, int hw, int c, dbsr_tensor in, dbsr_tensor gate, dbsr_
 /* torch.optim.Adam step (weight_decay 0) on flat fp32 buffers; grad is scaled by grad_scale first. */
 int dbsr_adam_step(long long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
                    float beta1, float beta2, float eps, int step, float grad_scale, void* stream);
+/* ---------------- dynamic loss scaling (csrc/loss_scale.hip; exports added under ABI 23) ----------------
+ * 16-bit training with torch.amp.GradScaler's rule, kept on the device: a step reads nothing back to the host
+ * (it replays as HIP graphs), so the scale, the overflow flag, the skip decision and Adam's step number live
+ * in one state buffer of DBSR_LS_WORDS 32-bit words (device memory, 4-B aligned, owned by the caller), which
+ * the four ops below read and write -- none takes the scale, the step number or the decision from the host.
+ *   word  type   field
+ *   0     float  scale           the loss scale S (dpre is S times the true gradient; > 0)
+ *   1     int    growth_tracker  clean steps since the scale last changed
+ *   2     int    found_inf       0 / 1: an inf or NaN was seen in this step's gradients
+ *   3     int    adam_step       optimizer steps actually applied (skipped steps do not count)
+ *   4     int    skipped         steps skipped because of an overflow
+ *   5..7         reserved (0)
+ * The caller initialises it once (scale, zeros) and may read it back for logging.  Order within a step, all on
+ * one stream: dbsr_l1_loss_backward_scaled (start of the backward) ... dbsr_grad_unscale_check (after the
+ * gradients are final and, across ranks, summed: a sum carries one rank's inf / NaN to every rank, so all ranks
+ * take the same decision) -> dbsr_adam_step_guarded -> dbsr_loss_scale_update. */
+enum { DBSR_LS_SCALE = 0, DBSR_LS_GROWTH_TRACKER = 1, DBSR_LS_FOUND_INF = 2, DBSR_LS_ADAM_STEP = 3,
+       DBSR_LS_SKIPPED = 4, DBSR_LS_WORDS = 8 };
+/* dbsr_l1_loss_backward with dpre multiplied by state.scale; *loss is the unscaled loss.  Both dpre paths of
+ * dbsr_l1_loss_backward (generic; 16-bit, ld 8, c0 0: one 16-B store per pixel).  With scale 1 loss and dpre are
+ * bitwise dbsr_l1_loss_backward's; a product beyond the compute dtype's range is stored as inf. */
+int dbsr_l1_loss_backward_scaled(int B, int C, int H, int W, int boundary_ignore, const float* pred, const float* gt,
+                                 const void* state, dbsr_tensor dpre, float* loss, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+/* grad[i] *= 1 / state.scale in place over n fp32 values (any n > 0, grad 4-B aligned: 16-B accesses over the
+ * aligned body, scalar ends); state.found_inf is set when any product is inf or NaN (tested on the bits),
+ * left as it is otherwise. */
+int dbsr_grad_unscale_check(long long n, float* grad, void* state, void* stream);
+/* dbsr_adam_step with step = state.adam_step + 1 read on the device; param, exp_avg and exp_avg_sq are left
+ * untouched when state.found_inf is set.  Does not write the state. */
+int dbsr_adam_step_guarded(long long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
+                           float beta1, float beta2, float eps, float grad_scale, const void* state, void* stream);
+/* End of a step (one thread).  found_inf set: scale *= backoff_factor, growth_tracker = 0, skipped += 1; else
+ * adam_step += 1, growth_tracker += 1 and, when it reaches growth_interval, scale *= growth_factor and
+ * growth_tracker = 0.  Then found_inf = 0.  Factors > 0 (1, 1: a fixed scale), growth_interval >= 1. */
+int dbsr_loss_scale_update(void* state, float growth_factor, float backoff_factor, int growth_interval, void* stream);
 /* wt[ci][co][ky][kx] = w[co][ci][kh-1-ky][kw-1-kx] (fp32): the dgrad conv's weights, to pack with
  * dbsr_conv_pack_weights(cout = cin, cin = cout). */
 int dbsr_dgrad_weights(const float* w, int cout, int cin, int kh, int kw, float* wt, void* stream);

@@ -7,7 +7,10 @@ the host and make the RAW bursts and the linear ground truth on the GPU, and giv
 smaller than crop + 2 * border (432 px) are skipped when the folder is listed.  The network starts from the seeded
 synthetic weights unless --weights names a state dict.
 
-Usage: python tools/train_synthetic.py IMAGE_DIR [--steps 100 --batch 16 --lr 1e-4 --seed 0 --save out.pth]"""
+--dtype picks the compute dtype (bf16 default; fp16 trains with DBSRTrainer's dynamic loss scaler, whose state is
+printed with the loss; fp32).
+
+Usage: python tools/train_synthetic.py IMAGE_DIR [--steps 100 --batch 16 --lr 1e-4 --seed 0 --dtype bf16 --save out.pth]"""
 import argparse
 import os
 import random
@@ -51,6 +54,7 @@ def main():
     ap.add_argument('--border-crop', type=int, default=24)
     ap.add_argument('--lr', type=float, default=1e-4)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--dtype', choices=['bf16', 'fp16', 'fp32'], default='bf16')
     ap.add_argument('--weights', default=None)
     ap.add_argument('--save', default=None)
     args = ap.parse_args()
@@ -68,7 +72,8 @@ def main():
     net = dbsr_amd.build_synthetic_net(seed=0)
     if args.weights:
         net.load_state_dict(torch.load(args.weights, map_location='cpu'))
-    net = net.to(dev).set_compute_dtype(torch.bfloat16)
+    dtype = {'bf16': torch.bfloat16, 'fp16': torch.float16, 'fp32': torch.float32}[args.dtype]
+    net = net.to(dev).set_compute_dtype(dtype)
     trainer = DBSRTrainer(net, lr=args.lr)
     btp = {'max_translation': args.max_translation, 'max_rotation': args.max_rotation, 'max_shear': 0.0,
            'max_scale': 0.0, 'border_crop': args.border_crop}
@@ -80,7 +85,9 @@ def main():
         d = proc([load_rgb8(random.choice(files)) for _ in range(args.batch)])
         loss = trainer.step(d['burst'], d['frame_gt'])
         if step % 10 == 0 or step == args.steps - 1:
-            print('step %d  loss %.5f' % (step, float(loss)), flush=True)
+            ls = trainer.loss_scale_state()          # (a small device-to-host copy: only where the loss is printed)
+            scaler = '' if ls is None else '  scale %g  applied %d  skipped %d' % (ls['scale'], ls['steps'], ls['skipped'])
+            print('step %d  loss %.5f%s' % (step, float(loss), scaler), flush=True)
     if args.save:
         torch.save(net.state_dict(), args.save)
 
