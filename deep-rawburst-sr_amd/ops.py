@@ -314,6 +314,110 @@ def chan_sum(t):
     return out
 
 
+# The ops below take the NHWC buffers the training plan passes ([images, ..., ld] device tensors, channels last,
+# `c` channels used from c0) and write their output buffer in place, so a caller chooses ld / c0 / padding itself.
+def _hw(t):
+    return t[0].numel() // t.shape[-1]
+
+
+def unshuffle_gate(ds, gate, du, s, c):
+    """dbsr_unshuffle_gate: ds / gate [B, H*s, W*s, ld] (c channels), du [B, H, W, ldu >= c*s*s] written in torch's
+    pixel_unshuffle channel order, du = unshuffle([gate > 0] * ds).  Returns du."""
+    _need_cuda(ds, gate, du)
+    B, H, W = du.shape[:3]
+    L.check(L.lib().dbsr_unshuffle_gate(B, H, W, s, c, L.tensor_desc(ds, ds.shape[-1]),
+                                        L.tensor_desc(gate, gate.shape[-1]), L.tensor_desc(du, du.shape[-1]),
+                                        L.stream_ptr(ds.device)), 'dbsr_unshuffle_gate')
+    return du
+
+
+def merge_prep_backward(dwp, proj, dproj, N, c):
+    """dbsr_merge_prep_backward: dwp [B*N, ..., ld >= 2c] (channels [0,c) d base, [c,2c) d diff), proj / dproj
+    [B*N, ..., ld >= c].  Returns dproj."""
+    _need_cuda(dwp, proj, dproj)
+    L.check(L.lib().dbsr_merge_prep_backward(dwp.shape[0] // N, N, _hw(dwp), c, L.tensor_desc(dwp, dwp.shape[-1]),
+                                             L.tensor_desc(proj, proj.shape[-1]),
+                                             L.tensor_desc(dproj, dproj.shape[-1]), L.stream_ptr(dwp.device)),
+            'dbsr_merge_prep_backward')
+    return dproj
+
+
+def gate_copy(inp, gate, out, c, out_c0=0, gate_map=L.IDENTITY):
+    """dbsr_gate_copy: out[f][.., out_c0 : out_c0 + c] = [gate[gate_map(f)] > 0] * inp[f] over inp's images.
+    Returns out."""
+    _need_cuda(inp, gate, out)
+    L.check(L.lib().dbsr_gate_copy(inp.shape[0], _hw(inp), c, L.tensor_desc(inp, inp.shape[-1]),
+                                   L.tensor_desc(gate, gate.shape[-1], fmap=gate_map),
+                                   L.tensor_desc(out, out.shape[-1], out_c0), L.stream_ptr(inp.device)),
+            'dbsr_gate_copy')
+    return out
+
+
+def enc_grad_gate(dref, dsrc32, e, de, N, c):
+    """dbsr_enc_grad_gate: dref [B, ..., ld], dsrc32 fp32 [B*N, ..., c] (dense), e / de [B*N, ..., ld]:
+    de[b*N+n] = [e > 0] * (n == 0 ? dref[b] : dsrc32[b*N+n]).  Returns de."""
+    _need_cuda(dref, dsrc32, e, de)
+    if dsrc32.dtype != torch.float32 or not dsrc32.is_contiguous() or dsrc32.shape[-1] != c:
+        raise ValueError('enc_grad_gate: dsrc32 must be a contiguous fp32 [B*N, ..., c] tensor')
+    L.check(L.lib().dbsr_enc_grad_gate(dref.shape[0], N, _hw(e), c, L.tensor_desc(dref, dref.shape[-1]),
+                                       dsrc32.data_ptr(), L.tensor_desc(e, e.shape[-1]),
+                                       L.tensor_desc(de, de.shape[-1]), L.stream_ptr(e.device)),
+            'dbsr_enc_grad_gate')
+    return de
+
+
+def relu_grad(pred, gout, dpre):
+    """dbsr_relu_grad: pred / gout fp32 NCHW [B,C,H,W] -> dpre [B,H,W,ld >= C] = [pred > 0] * gout in dpre's dtype
+    (channels C.. of dpre are left as they are).  Returns dpre."""
+    _need_cuda(pred, gout, dpre)
+    B, C, H, W = pred.shape
+    pred, gout = _f32c(pred), _f32c(gout)
+    L.check(L.lib().dbsr_relu_grad(B, C, H, W, pred.data_ptr(), gout.data_ptr(), L.tensor_desc(dpre, dpre.shape[-1]),
+                                   L.stream_ptr(pred.device)), 'dbsr_relu_grad')
+    return dpre
+
+
+def head_backward(h, dp, w, hc, dh):
+    """dbsr_head_backward: h / dh [n, ..., ld >= 32], dp [n, ..., 8] (hc channels used), w fp32 [hc, 32]: dh (in
+    place) = [h > 0] * (w^T . dp).  Returns (dh, dw fp32 [hc, 32], db fp32 [hc])."""
+    _need_cuda(h, dp, w, dh)
+    dev = h.device
+    n, hw = h.shape[0], _hw(h)
+    wd = w.reshape(hc, 32).to(torch.float32).contiguous()
+    dw = torch.zeros(hc, 32, dtype=torch.float32, device=dev)
+    db = torch.zeros(hc, dtype=torch.float32, device=dev)
+    need = L.lib().dbsr_head_backward_workspace_bytes(n, hw, 32, hc)
+    ws = torch.empty(need // 4 + 1, dtype=torch.float32, device=dev)
+    L.check(L.lib().dbsr_head_backward(n, hw, L.tensor_desc(h, h.shape[-1]), 32, L.tensor_desc(dp, dp.shape[-1]),
+                                       wd.data_ptr(), hc, L.tensor_desc(dh, dh.shape[-1]), dw.data_ptr(),
+                                       db.data_ptr(), 0, ws.data_ptr(), need, L.stream_ptr(dev)),
+            'dbsr_head_backward')
+    return dh, dw, db
+
+
+def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, n=None):
+    """dbsr_adam_step on the first n (default: all) elements of flat contiguous fp32 device tensors, in place."""
+    _need_cuda(param, grad, exp_avg, exp_avg_sq)
+    n = param.numel() if n is None else int(n)
+    for t in (param, grad, exp_avg, exp_avg_sq):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n:
+            raise ValueError('adam_step: contiguous fp32 tensors of at least n elements')
+    L.check(L.lib().dbsr_adam_step(n, param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                                   float(lr), float(betas[0]), float(betas[1]), float(eps), int(step),
+                                   float(grad_scale), L.stream_ptr(param.device)), 'dbsr_adam_step')
+
+
+def dgrad_weights(weight):
+    """dbsr_dgrad_weights: fp32 [cout, cin, kh, kw] -> [cin, cout, kh, kw], transposed and spatially flipped."""
+    _need_cuda(weight)
+    cout, cin, kh, kw = weight.shape
+    w32 = weight.to(torch.float32).contiguous()
+    wt = torch.empty(cin, cout, kh, kw, dtype=torch.float32, device=weight.device)
+    L.check(L.lib().dbsr_dgrad_weights(w32.data_ptr(), cout, cin, kh, kw, wt.data_ptr(), L.stream_ptr(weight.device)),
+            'dbsr_dgrad_weights')
+    return wt
+
+
 # ---------------------------------------------------------------------------------------------------
 # real-world fine-tuning objective (csrc/sca_train.hip; dbsr_hip.h 'real-world fine-tuning objective')
 # ---------------------------------------------------------------------------------------------------

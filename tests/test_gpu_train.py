@@ -29,7 +29,22 @@ def _rel(a, b):
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-12))
 
 
-@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+def _fp16_bounds(out, ref, r, sel=None):
+    """An fp16 output against the fp32 reference on the same rounded operands, r round-to-nearest steps between
+    the fp32 accumulator and the store: max|out - ref| <= (r 2^-11 + 1e-4) max|ref| (half an ulp per rounding plus
+    the fp32 summation-order term of the fp32 rows) and, over the elements `sel` (the open gates; all by default),
+    mean|out - ref| <= 2^-11 mean|ref| -- round-to-nearest averages a quarter ulp, about 1.7e-4 |ref| per step,
+    where a path that rounds like bf16 (8 bits) gives about 7e-4 |ref|."""
+    err = (out - ref).abs()
+    sel = torch.ones_like(ref, dtype=torch.bool) if sel is None else sel
+    mx, mean, rmean = float(err.max()), float(err[sel].mean()), float(ref[sel].abs().mean())
+    print('fp16 max err %.3g of max|ref| (bound %.3g), mean err %.3g of mean|ref| (bound %.3g)'
+          % (mx / float(ref.abs().max()), r * 2.0 ** -11 + 1e-4, mean / rmean, 2.0 ** -11))
+    assert mx <= (r * 2.0 ** -11 + 1e-4) * float(ref.abs().max())
+    assert mean <= 2.0 ** -11 * rmean
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize('case', [(2, 64, 20, 36, 64, 3), (1, 4, 9, 17, 64, 3), (2, 512, 8, 16, 64, 1),
                                   (1, 32, 24, 40, 3, 1), (1, 128, 12, 12, 512, 3), (2, 192, 16, 16, 128, 3),
                                   (3, 32, 20, 36, 32, 3), (1, 32, 33, 47, 3, 3), (2, 24, 16, 40, 32, 1)])
@@ -62,7 +77,7 @@ def test_conv_wgrad(ops, dtype, case):
     assert float((ob.cpu() - db).abs().max()) <= 1e-5 * float(dyr.abs().sum((0, 2, 3)).max())
 
 
-@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize('case', [(2, 64, 20, 36, 64, 3), (1, 64, 12, 16, 4, 3), (2, 64, 8, 16, 512, 1),
                                   (1, 3, 24, 40, 32, 1), (1, 512, 12, 12, 64, 3)])
 def test_conv_dgrad_gate_residual(ops, dtype, case):
@@ -73,14 +88,18 @@ def test_conv_dgrad_gate_residual(ops, dtype, case):
     w = torch.randn(Cout, Cin, k, k, generator=gen) / (Cin * k * k) ** 0.5
     res = torch.randn(N, Cin, H, W, generator=gen)
     gate = F.relu(torch.randn(N, Cin, H, W, generator=gen))
-    dyr, wr, rr = (t.to(dtype).float() for t in (dy, w, res))
+    dyr, wr, rr, gr = (t.to(dtype).float() for t in (dy, w, res, gate))
     x = torch.zeros(N, Cin, H, W, requires_grad=True)
     F.conv2d(x, wr, padding=k // 2).backward(dyr)
-    ref = (x.grad + rr) * (gate > 0)
+    ref = (x.grad + rr) * (gr > 0)
     out = ops.conv2d_dgrad(dy.to(DEV), w.to(DEV), residual=res.to(DEV), gate=gate.to(DEV),
                            compute_dtype=dtype).float().cpu()
     tol = 1e-4 if dtype == torch.float32 else 2e-2
     assert _rel(out, ref) <= tol
+    if dtype == torch.float16:
+        # every epilogue adds the residual to the fp32 accumulator and rounds once (r = 1); + 1 for the residual,
+        # since |conv| may exceed |conv + residual|
+        _fp16_bounds(out, ref, 2, gr > 0)
 
 
 # (N, Cout, H, W, Cin, expected kernel): the gated (training dgrad) epilogues of the fast kernels -- weight-
@@ -92,33 +111,38 @@ GATED = [(12, 64, 48, 48, 64, 4), (40, 64, 32, 16, 96, 4), (48, 128, 48, 48, 64,
          (64, 128, 32, 32, 96, 2)]
 
 
-@pytest.mark.parametrize('case', GATED)
+# the bf16 rows first (cases 0-4 as before), then the same rows, the same kernels expected, in fp16
+@pytest.mark.parametrize('case', [c + (torch.bfloat16,) for c in GATED] + [c + (torch.float16,) for c in GATED])
 def test_conv_dgrad_gated_fast_kernels(ops, case):
     """the gated epilogues the training step runs at 48x48 / 128x128 against autograd, with the
-    kernel asserted (dbsr_conv_kernel_for), with and without the ResBlock residual."""
-    N, Cout, H, W, Cin, kern = case
-    dtype = torch.bfloat16
+    kernel asserted (dbsr_conv_kernel_for; the same kernel for bf16 and fp16), with and without the ResBlock
+    residual."""
+    N, Cout, H, W, Cin, kern, dtype = case
     gen = torch.Generator().manual_seed(Cin * 7 + Cout + W)
     dy = torch.randn(N, Cout, H, W, generator=gen)
     w = torch.randn(Cout, Cin, 3, 3, generator=gen) / (Cin * 9) ** 0.5
     res = torch.randn(N, Cin, H, W, generator=gen)
     gate = F.relu(torch.randn(N, Cin, H, W, generator=gen))
-    dyr, wr, rr = (t.to(dtype).float() for t in (dy, w, res))
+    dyr, wr, rr, gr = (t.to(dtype).float() for t in (dy, w, res, gate))
     x = torch.zeros(N, Cin, H, W, requires_grad=True)
     F.conv2d(x, wr, padding=1).backward(dyr)
     for use_res in (True, False):
-        ref = ((x.grad + rr) if use_res else x.grad) * (gate > 0)
+        ref = ((x.grad + rr) if use_res else x.grad) * (gr > 0)
         out = ops.conv2d_dgrad(dy.to(DEV), w.to(DEV), residual=res.to(DEV) if use_res else None, gate=gate.to(DEV),
                                compute_dtype=dtype).float().cpu()
         assert ops.conv2d_dgrad.last_kernel == kern, (case, ops.conv2d_dgrad.last_kernel)
         assert _rel(out, ref) <= 2e-2
-        assert bool(((out != 0) <= (gate > 0)).all())           # gated-off outputs are exactly zero
+        assert bool(((out != 0) <= (gr > 0)).all())             # gated-off outputs are exactly zero
+        if dtype == torch.float16:
+            _fp16_bounds(out, ref, 2 if use_res else 1, gr > 0)     # one rounding (+ 1 with the residual)
 
 
-@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
-def test_fuse_backward(ops, dtype):
+# shape = (N, C, H, W).  N = 1 has no `oth` tensor; fuse_bwd_kernel works in frame chunks of 7, so N = 7 is exactly
+# one chunk, 8 one frame into the second chunk and 15 two chunks plus one (the workload's 14 lies between)
+def _fuse_backward_case(ops, dtype, shape):
     gen = torch.Generator().manual_seed(3)
-    B, N, C, H, W = 2, 5, 64, 6, 7
+    B = 2
+    N, C, H, W = shape
     lg = torch.randn(B, N, C, H, W, generator=gen)
     f = torch.randn(B, N, C, H, W, generator=gen)
     df = torch.randn(B, C, H, W, generator=gen)
@@ -128,9 +152,41 @@ def test_fuse_backward(ops, dtype):
     fused.backward(df.to(dtype).float())
     dl, dfe = ops.fuse_backward(w.detach().to(DEV).to(dtype), f.to(DEV).to(dtype), fused.detach().to(DEV).to(dtype),
                                 df.to(DEV).to(dtype))
-    tol = 1e-5 if dtype == torch.float32 else 3e-2
-    assert _rel(dl.float().cpu(), lgr.grad) <= tol
-    assert _rel(dfe.float().cpu(), fr.grad) <= tol
+    dl, dfe = dl.float().cpu(), dfe.float().cpu()
+    if dtype != torch.float16:
+        tol = 1e-5 if dtype == torch.float32 else 3e-2
+        assert _rel(dl, lgr.grad) <= tol
+        assert _rel(dfe, fr.grad) <= tol
+    if dtype != torch.float32:
+        # the kernel's inputs are the *rounded* weights and fused features, which autograd through the fp32 softmax
+        # does not see: the closed form (merging.py:116-124; dF_n = w_n dfused, dl_n = w_n dfused (f_n - fused)) in
+        # fp64 on exactly the rounded operands -- checked against autograd on unrounded ones first
+        w64, fu64, f64, df64 = (t.detach().double() for t in (w, fused, fr, df.to(dtype).float()))
+        assert _rel((w64 * df64[:, None]).float(), fr.grad) <= 1e-5
+        assert _rel((w64 * df64[:, None] * (f64 - fu64[:, None])).float(), lgr.grad) <= 1e-5
+        wq, fuq = w.detach().to(dtype).double(), fused.detach().to(dtype).double()
+        rdf = (wq * df64[:, None]).float()
+        rdl = (wq * df64[:, None] * (f64 - fuq[:, None])).float()
+        if dtype == torch.float16:
+            # fp32 products of rounded factors, one rounding at the store (r = 1)
+            _fp16_bounds(dfe, rdf, 1)
+            if N > 1:
+                _fp16_bounds(dl, rdl, 1)
+            else:
+                assert not bool(dl.any()) and not bool(rdl.any())     # one frame: f == fused, dl is exactly 0
+        else:
+            assert _rel(dfe, rdf) <= 2.0 ** -8 + 1e-4 and _rel(dl, rdl) <= 2.0 ** -8 + 1e-4
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
+def test_fuse_backward(ops, dtype):
+    _fuse_backward_case(ops, dtype, (5, 64, 6, 7))
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize('N', [1, 7, 8, 15])
+def test_fuse_backward_frame_chunks(ops, dtype, N):
+    _fuse_backward_case(ops, dtype, (N, 8, 5, 7))
 
 
 def test_warp_backward(ops):
@@ -144,7 +200,7 @@ def test_warp_backward(ops):
     assert _rel(out, x.grad) <= 1e-5
 
 
-@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize('case', [(2, 3, 40, 56), (3, 32, 64, 64), (2, 64, 17, 23), (1, 512, 12, 20), (1, 72, 9, 9)])
 def test_chan_sum(ops, dtype, case):
     """Bias gradient (per-channel sum): the 16-B kernel (16-bit, any c) and the element kernel (fp32)."""
@@ -155,7 +211,7 @@ def test_chan_sum(ops, dtype, case):
     assert float((out.double() - ref).abs().max()) <= 1e-4 * float(t.double().abs().sum(dim=(0, 2, 3)).max())
 
 
-@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize('case', [(2, 40, 56, 3), (1, 33, 47, 3), (3, 16, 16, 1), (1, 64, 64, 4)])
 def test_head_forward_backward(dtype, case):
     """The training step's predictor (dbsr_head_forward / dbsr_head_backward; decoders.py:61, 1x1 conv 32 -> hc +
@@ -194,6 +250,8 @@ def test_head_forward_backward(dtype, case):
     got = dh.float().cpu().permute(0, 3, 1, 2)
     tol = 1e-4 if dtype == torch.float32 else 1e-2                  # dh is stored in the compute dtype
     assert float((got - gh).abs().max()) <= tol * float(gh.abs().max())
+    if dtype == torch.float16:
+        _fp16_bounds(got, gh, 1, h > 0)                              # the fp32 sum over hc, rounded at the store
     assert _rel(dw.cpu(), ww.grad.reshape(hc, 32)) <= 1e-4
     assert float((db.cpu() - bb.grad).abs().max()) <= 1e-5 * float(dp.abs().sum((0, 2, 3)).max())
 
@@ -201,7 +259,8 @@ def test_head_forward_backward(dtype, case):
 @pytest.mark.parametrize('case', [(3, 16, 12, 20, 3.0, torch.float32, False),     # random flow: list flushes
                                   (2, 64, 40, 56, 20.0, torch.float32, True),     # far taps, window = frame
                                   (2, 72, 33, 47, 0.7, torch.float32, True),      # ragged tiles, C % 64 != 0
-                                  (2, 64, 32, 48, 2.0, torch.bfloat16, True)])
+                                  (2, 64, 32, 48, 2.0, torch.bfloat16, True),
+                                  (2, 64, 32, 48, 2.0, torch.float16, True)])
 def test_warp_backward_gather(ops, case):
     """The owner-computes gather (no atomics) against autograd through the oracle's grid_sample warp,
     with the encoder-ReLU gate of the training step."""
@@ -217,6 +276,8 @@ def test_warp_backward_gather(ops, case):
     out = ops.warp_backward_gather(dy.to(DEV).to(dtype), fl.to(DEV), gate.to(DEV) if gated else None).float().cpu()
     tol = 1e-5 if dtype == torch.float32 else 8e-3
     assert _rel(out, ref) <= tol
+    if dtype == torch.float16:
+        _fp16_bounds(out, ref, 1, gate.float() > 0)                 # the pixel's fp32 sum, rounded at the store
 
 
 @pytest.mark.parametrize('converge', [False, True])
