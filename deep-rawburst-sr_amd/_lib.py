@@ -167,6 +167,12 @@ def lib():
             'dbsr_warp_backward_gather': ([c_int, c_int, c_int, c_int, Tensor, c_void_p, c_ll, Tensor, Tensor, c_void_p,
                                            c_size_t, c_void_p], c_int),
             'dbsr_gate_copy': ([c_int, c_int, c_int, Tensor, Tensor, Tensor, c_void_p], c_int),
+            'dbsr_warp_flow_backward': ([c_int, c_int, c_int, c_int, Tensor, Tensor, c_void_p, c_ll, c_void_p, c_ll,
+                                         c_int, c_void_p], c_int),
+            'dbsr_backwarp_backward': ([c_int, c_int, c_int, c_int, Tensor, Tensor, c_float, Tensor, Tensor, Tensor,
+                                        c_void_p], c_int),
+            'dbsr_offsets_export': ([c_int, c_int, c_int, c_int, c_void_p, c_ll, c_void_p, c_float, Tensor, c_void_p],
+                                    c_int),
             'dbsr_adam_step': ([c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int,
                                 c_float, c_void_p], c_int),
             'dbsr_l1_loss_backward_scaled': ([c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, Tensor,
@@ -229,6 +235,7 @@ EXPORTED = ['dbsr_abi_version', 'dbsr_last_error', 'dbsr_conv_packed_elems', 'db
             'dbsr_chan_sum_workspace_bytes', 'dbsr_chan_sum', 'dbsr_l1_loss_backward', 'dbsr_relu_grad', 'dbsr_unshuffle_gate',
             'dbsr_fuse_backward', 'dbsr_merge_prep_backward', 'dbsr_warp_backward', 'dbsr_enc_grad_gate',
             'dbsr_warp_backward_gather_workspace_bytes', 'dbsr_warp_backward_gather', 'dbsr_gate_copy',
+            'dbsr_warp_flow_backward', 'dbsr_backwarp_backward', 'dbsr_offsets_export',
             'dbsr_adam_step', 'dbsr_dgrad_weights',
             'dbsr_l1_loss_backward_scaled', 'dbsr_grad_unscale_check', 'dbsr_adam_step_guarded',
             'dbsr_loss_scale_update',

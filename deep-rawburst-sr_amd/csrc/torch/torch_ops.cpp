@@ -9,11 +9,13 @@
 //   dbsr::backwarp(input, flow)                    models/alignment/pwcnet.py:16-38
 //   dbsr::warp_bilinear(feat, flow)                models/layers/warp.py:19-46
 //   dbsr::warp_bilinear_backward(grad, flow)       (grid_sample backward w.r.t. the features)
+//   dbsr::warp_bilinear_flow_backward(grad, feat, flow)   (grid_sample backward w.r.t. the flow)
+//   dbsr::backwarp_backward(grad, input, flow, need_input, need_flow)   (w.r.t. both; the mask takes none)
 //   dbsr::fuse_softmax(logits, feats, want_weights) models/dbsr/merging.py:116-126
 //   dbsr::fuse_backward(weights, feats, fused, dfused)
 //   dbsr::conv2d_fused(x, w, b, stride, padding, dilation, act, residual, post_act)
 //                                                  nn.Conv2d + models/layers/blocks.py:46-96 epilogues
-// Autograd formulas for correlation / warp / fusion are registered from Python (dbsr_amd/torch_ops.py)
+// Autograd formulas for correlation / backwarp / warp / fusion are registered from Python (dbsr_amd/torch_ops.py)
 // with torch.library.register_autograd on top of the *_backward ops.
 #include <ATen/ATen.h>
 #include <ATen/hip/HIPContext.h>
@@ -144,6 +146,45 @@ at::Tensor warp_bilinear_backward(const at::Tensor& grad, const at::Tensor& flow
                              dbsr_frame_map{1, 1, 0, 1}, H * W * r8(C), cur_stream()),
           "dbsr_warp_backward");
     return nchw(out, C).to(grad.scalar_type());
+}
+
+at::Tensor warp_bilinear_flow_backward(const at::Tensor& grad, const at::Tensor& feat, const at::Tensor& flow) {
+    need_hip(grad, "warp_bilinear_flow_backward");
+    TORCH_CHECK(feat.dim() == 4 && grad.sizes() == feat.sizes() && flow.dim() == 4 && flow.size(1) == 2,
+                "dbsr::warp_bilinear_flow_backward: grad / feat [N,C,H,W], flow [N,2,H,W]");
+    const int64_t N = feat.size(0), C = feat.size(1), H = feat.size(2), W = feat.size(3);
+    const auto dt = feat.scalar_type();
+    auto x = nhwc(feat, r8(C), dt), g = nhwc(grad, r8(C), dt);
+    auto fl = flow.to(at::kFloat).contiguous();
+    auto out = at::empty({N, 2, H, W}, feat.options().dtype(at::kFloat));
+    check(dbsr_warp_flow_backward(N, H, W, r8(C), desc(x, r8(C)), desc(g, r8(C)), fl.data_ptr<float>(), 2 * H * W,
+                                  out.data_ptr<float>(), 2 * H * W, 0, cur_stream()),
+          "dbsr_warp_flow_backward");
+    return out.to(flow.scalar_type());
+}
+
+// (an unwanted gradient is returned as an empty tensor and is not computed)
+std::tuple<at::Tensor, at::Tensor> backwarp_backward(const at::Tensor& grad, const at::Tensor& input,
+                                                     const at::Tensor& flow, bool need_input, bool need_flow) {
+    need_hip(grad, "backwarp_backward");
+    TORCH_CHECK(input.dim() == 4 && grad.sizes() == input.sizes() && flow.dim() == 4 && flow.size(1) == 2,
+                "dbsr::backwarp_backward: grad / input [N,C,H,W], flow [N,2,H,W]");
+    const int64_t N = input.size(0), C = input.size(1), H = input.size(2), W = input.size(3);
+    const auto dt = input.scalar_type();
+    at::Tensor din = at::empty({0}, input.options()), dfl = at::empty({0}, flow.options());
+    if (!need_input && !need_flow) return {din, dfl};
+    auto x = nhwc(input, r8(C), dt), g = nhwc(grad, r8(C), dt);
+    auto fl = flow.permute({0, 2, 3, 1}).to(at::kFloat).contiguous();
+    at::Tensor di32, df32;
+    if (need_input) di32 = at::empty({N, H, W, r8(C)}, input.options().dtype(at::kFloat));
+    if (need_flow) df32 = at::empty({N, H, W, 2}, input.options().dtype(at::kFloat));
+    check(dbsr_backwarp_backward(N, H, W, C, desc(x, r8(C)), desc(fl, 2), 1.0f, desc(g, r8(C)),
+                                 need_input ? desc(di32, r8(C)) : null_desc(), need_flow ? desc(df32, 2) : null_desc(),
+                                 cur_stream()),
+          "dbsr_backwarp_backward");
+    if (need_input) din = nchw(di32, C).to(dt);
+    if (need_flow) dfl = nchw(df32, 2).to(flow.scalar_type());
+    return {din, dfl};
 }
 
 // feats [B,N,C,H,W] (frame 0 = the reference), logits [B,N,C,H,W] -> (fused [B,C,H,W], weights [B,N,C,H,W])
@@ -324,6 +365,9 @@ TORCH_LIBRARY(dbsr, m) {
     m.def("backwarp(Tensor input, Tensor flow) -> Tensor");
     m.def("warp_bilinear(Tensor feat, Tensor flow) -> Tensor");
     m.def("warp_bilinear_backward(Tensor grad, Tensor flow) -> Tensor");
+    m.def("warp_bilinear_flow_backward(Tensor grad, Tensor feat, Tensor flow) -> Tensor");
+    m.def("backwarp_backward(Tensor grad, Tensor input, Tensor flow, bool need_input=True, bool need_flow=True) -> "
+          "(Tensor, Tensor)");
     m.def("fuse_softmax(Tensor logits, Tensor feats, bool want_weights=True) -> (Tensor, Tensor)");
     m.def("fuse_backward(Tensor weights, Tensor feats, Tensor fused, Tensor dfused) -> (Tensor, Tensor)");
     m.def("conv2d_fused(Tensor x, Tensor weight, Tensor? bias=None, int stride=1, int padding=0, int dilation=1, "
@@ -341,6 +385,8 @@ TORCH_LIBRARY_IMPL(dbsr, CUDA, m) {
     m.impl("backwarp", &backwarp);
     m.impl("warp_bilinear", &warp_bilinear);
     m.impl("warp_bilinear_backward", &warp_bilinear_backward);
+    m.impl("warp_bilinear_flow_backward", &warp_bilinear_flow_backward);
+    m.impl("backwarp_backward", &backwarp_backward);
     m.impl("fuse_softmax", &fuse_softmax);
     m.impl("fuse_backward", &fuse_backward);
     m.impl("conv2d_fused", &conv2d_fused);

@@ -130,14 +130,19 @@ class DBSRNet(nn.Module):
             return False
         return any(p.requires_grad for n, p in self.named_parameters() if not n.startswith('encoder.alignment_net'))
 
-    def forward(self, im):
+    def forward(self, im, flow=None):
+        """flow: offsets [B,N-1,2,H,W] from the caller's own alignment network instead of the package's PWC-Net
+        (training mode only; differentiable: loss.backward() reaches the module that produced it)."""
         if im.dim() != 5:
             raise ValueError('expected burst [B,N,4,H,W], got shape {}'.format(tuple(im.shape)))
         if self._trains():
             # autograd through the HIP training forward / backward (training.train_forward): the reference's
             # loop -- pred, _ = net(burst); loss.backward(); optimizer.step() -- runs unchanged
             from .training import train_forward
-            return train_forward(self, im)
+            return train_forward(self, im, flow)
+        if flow is not None:
+            raise NotImplementedError('DBSRNet.forward(flow=...): the inference engine takes no external flows; '
+                                      'DBSRTrainer.forward_saved(burst, flow=flow) runs the forward with them')
         return self._get_engine().forward(im)
 
 

@@ -299,6 +299,46 @@ def warp_backward_gather(dout, flow, gate=None):
     return out.permute(0, 3, 1, 2).contiguous()
 
 
+def warp_flow_backward(feat, dout, flow):
+    """dL/dflow of warp(feat, flow) (warp.py:19-46): feat, dout [N,C,H,W] of one dtype (fp32 / bf16 / fp16),
+    flow [N,2,H,W] -> fp32 [N,2,H,W]."""
+    _need_cuda(feat, dout, flow)
+    N, C, H, W = feat.shape
+    ld = (C + 7) // 8 * 8
+    x = torch.zeros(N, H, W, ld, dtype=feat.dtype, device=feat.device)
+    x[..., :C] = feat.permute(0, 2, 3, 1)
+    d = torch.zeros_like(x)
+    d[..., :C] = dout.permute(0, 2, 3, 1)
+    fl = flow.to(torch.float32).contiguous()
+    out = torch.empty(N, 2, H, W, dtype=torch.float32, device=feat.device)
+    L.check(L.lib().dbsr_warp_flow_backward(N, H, W, ld, L.tensor_desc(x, ld), L.tensor_desc(d, ld), fl.data_ptr(),
+                                            2 * H * W, out.data_ptr(), 2 * H * W, 0, L.stream_ptr(feat.device)),
+            'dbsr_warp_flow_backward')
+    return out
+
+
+def backwarp_backward(inp, flow, dout, scale=1.0, need_input=True, need_flow=True):
+    """(dL/dinput, dL/dflow) of backwarp(input, flow * scale) (pwcnet.py:16-38; the mask carries no gradient):
+    inp, dout [N,C,H,W], flow [N,2,H,W] -> (fp32 [N,C,H,W], fp32 [N,2,H,W]); an unwanted one is None and costs
+    nothing."""
+    _need_cuda(inp, flow, dout)
+    if not (need_input or need_flow):
+        return None, None
+    N, C, H, W = inp.shape
+    x, ldx = _nhwc(inp)
+    d, _ = _nhwc(dout, inp.dtype)
+    fl = flow.permute(0, 2, 3, 1).to(torch.float32).contiguous()
+    din = torch.empty(N, H, W, ldx, dtype=torch.float32, device=inp.device) if need_input else None
+    dfl = torch.empty(N, H, W, 2, dtype=torch.float32, device=inp.device) if need_flow else None
+    L.check(L.lib().dbsr_backwarp_backward(N, H, W, C, L.tensor_desc(x, ldx), L.tensor_desc(fl, 2), float(scale),
+                                           L.tensor_desc(d, ldx),
+                                           L.tensor_desc(din, ldx) if need_input else L.NULL_TENSOR,
+                                           L.tensor_desc(dfl, 2) if need_flow else L.NULL_TENSOR,
+                                           L.stream_ptr(inp.device)), 'dbsr_backwarp_backward')
+    return (din[..., :C].permute(0, 3, 1, 2).contiguous() if need_input else None,
+            dfl.permute(0, 3, 1, 2).contiguous() if need_flow else None)
+
+
 def chan_sum(t):
     """Per-channel sum over batch and pixels (the conv bias gradient) of t [N,C,H,W] -> fp32 [C]."""
     _need_cuda(t)

@@ -8,12 +8,15 @@ way the reference's _FunctionCorrelation does (external/pwcnet/correlation/corre
                                                                 leaky_relu with leaky=True)
     torch.ops.dbsr.backwarp(input, flow)                        pwcnet.py:16-38
     torch.ops.dbsr.warp_bilinear(feat, flow)                    warp.py:19-46
+    torch.ops.dbsr.warp_bilinear_flow_backward(grad, feat, flow)   warp's gradient w.r.t. the flow
+    torch.ops.dbsr.backwarp_backward(grad, input, flow)         backwarp's gradients -> (dinput, dflow)
     torch.ops.dbsr.fuse_softmax(logits, feats, want_weights)    merging.py:116-126 -> (fused, weights)
     torch.ops.dbsr.conv2d_fused(x, w, b, stride, padding, dilation, act, residual, post_act)
 
-Gradients: correlation w.r.t. both inputs (K3/K4), warp and fusion w.r.t. the features / logits (the
-flow is the frozen PWC-Net's output and takes none, encoders.py:56-61).  No CPU kernels: like the
-reference's correlation (correlation.py:324-325) the ops raise on CPU tensors.
+Gradients: correlation w.r.t. both inputs (K3/K4), backwarp and warp w.r.t. the sampled tensor and the flow
+(csrc/flow_grad.hip; backwarp's in-place thresholded mask takes none, pwcnet.py:33-38), fusion w.r.t. the
+features / logits.  Only the gradients autograd asks for are computed.  No CPU kernels: like the reference's
+correlation (correlation.py:324-325) the ops raise on CPU tensors.
 """
 import os
 
@@ -56,13 +59,33 @@ def _register_autograd():
     lib.register_autograd('dbsr::correlation', corr_bwd, setup_context=corr_setup)
 
     def warp_setup(ctx, inputs, output):
-        ctx.save_for_backward(inputs[1])
+        feat, flow = inputs
+        # the features are needed only for the flow's gradient
+        ctx.save_for_backward(flow, feat if ctx.needs_input_grad[1] else None)
 
     def warp_bwd(ctx, grad):
-        (flow,) = ctx.saved_tensors
-        return torch.ops.dbsr.warp_bilinear_backward(grad.contiguous(), flow), None
+        flow, feat = ctx.saved_tensors
+        grad = grad.contiguous()
+        dfeat = torch.ops.dbsr.warp_bilinear_backward(grad, flow) if ctx.needs_input_grad[0] else None
+        dflow = torch.ops.dbsr.warp_bilinear_flow_backward(grad, feat, flow) \
+            if ctx.needs_input_grad[1] and feat is not None else None
+        return dfeat, dflow
 
     lib.register_autograd('dbsr::warp_bilinear', warp_bwd, setup_context=warp_setup)
+
+    def backwarp_setup(ctx, inputs, output):
+        inp, flow = inputs
+        ctx.save_for_backward(inp if ctx.needs_input_grad[1] else None, flow)
+
+    def backwarp_bwd(ctx, grad):
+        inp, flow = ctx.saved_tensors
+        need_in, need_fl = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and inp is not None
+        if inp is None:                       # only d/d(input): the kernel does not read the input then
+            inp = grad
+        din, dfl = torch.ops.dbsr.backwarp_backward(grad.contiguous(), inp, flow, need_in, need_fl)
+        return (din if need_in else None), (dfl if need_fl else None)
+
+    lib.register_autograd('dbsr::backwarp', backwarp_bwd, setup_context=backwarp_setup)
 
     def fuse_setup(ctx, inputs, output):
         logits, feats, want = inputs

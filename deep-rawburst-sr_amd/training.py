@@ -114,6 +114,12 @@ class DBSRTrainer:
     re-pointed into one flat fp32 buffer (the optimizer's master copy; the module sees the updates);
     `flat_grad` holds the step's gradients in the same layout (decoder first, then merging, then
     encoder: the order the backward completes them, so the bucketed all-reduce can start early).
+
+    flow_grad=True: the backward goes on to dL/d(offsets) -- the offset-feature extractor's first conv back to its
+    2-channel input plus the warp's flow gradient (csrc/flow_grad.hip) -- and flow_grad() returns it, fp32
+    [B,N-1,2,H,W] (unscaled when a loss scaler runs).  step / forward_backward / forward_saved take `flow`
+    ([B,N-1,2,H,W] fp32 on the device): the offsets then come from the caller (an alignment network of their own)
+    instead of the package's PWC-Net, in a plan of its own without PWC-Net ops.
     """
     # re-pack every conv's weights in one launch (dbsr_conv_pack_weights_batch, bitwise the per-conv
     # pack / dgrad-transpose / pack launches it replaces: False runs those, for A/B and the equality test)
@@ -124,11 +130,13 @@ class DBSRTrainer:
 
     def __init__(self, net, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, boundary_ignore=40, process_group=None,
                  bucket_bytes=4 << 20, optimizer=True, loss_scale=None, init_scale=65536.0, growth_factor=2.0,
-                 backoff_factor=0.5, growth_interval=2000):
+                 backoff_factor=0.5, growth_interval=2000, flow_grad=False):
         dev = next(net.parameters()).device
         if dev.type != 'cuda':
             raise RuntimeError('DBSRTrainer needs the network on a HIP device')
         self.net, self.dev, self.dtype = net, dev, net.compute_dtype
+        self.want_flow_grad = bool(flow_grad)
+        self._flow_plan = None            # the plan whose dflow buffer holds the last backward's dL/d(offsets)
         # Loss scaling (csrc/loss_scale.hip, torch.amp.GradScaler's rule on the device).  None: no scaling -- the
         # plan and the optimizer launch are the unscaled ones -- except for an fp16 net, where it means 'dynamic':
         # the L1 gradient 1/count (~4.7e-8 at configs[3]) is below fp16's smallest subnormal, so an unscaled
@@ -160,8 +168,9 @@ class DBSRTrainer:
             self._fb_inf = torch.zeros(1, dtype=torch.int32, device=dev)   # found_inf of the last forward_backward
         self.lr, self.betas, self.eps, self.bi = lr, betas, eps, boundary_ignore
         if getattr(net.encoder, 'train_alignmentnet', False):
-            # the reference then backpropagates into PWC-Net (encoders.py:56-57); the HIP backward stops at the
-            # flows, so refuse rather than train without alignment gradients
+            # the reference then backpropagates into PWC-Net (encoders.py:56-57); the HIP backward reaches
+            # dL/d(offsets) (flow_grad=True) but PWC-Net itself runs forward-only here, so refuse rather than train
+            # without alignment gradients (an alignment network in torch trains through the `flow` argument)
             raise NotImplementedError('DBSRTrainer: train_alignmentnet=True (PWC-Net training) is not on the HIP '
                                       'backward; build the net with train_alignmentnet=False (dbsrnet_cvpr2021 default)')
         softmax, ref_base, self.offset_modulo = merging_variant(net.merging)
@@ -253,8 +262,9 @@ class DBSRTrainer:
             tc.name = names[id(tc.mod)]
 
     # ------------------------------------------------------------------------------------------------
-    def _build(self, B, N, H, W):
+    def _build(self, B, N, H, W, ext_flow=False, flow_grad=None):
         dt, dev, lib = self.dtype, self.dev, L.lib()
+        flow_grad = self.want_flow_grad if flow_grad is None else bool(flow_grad)
         plan = Plan()
         plan.lane = 0
         F, P = B * N, B * (N - 1)
@@ -299,15 +309,28 @@ class DBSRTrainer:
                 tc.repack_ops(plan)
         raw = NHWC(F, H, W, 8, dt, dev)
         Hp, Wp = int(math.ceil(H / 64.0) * 64), int(math.ceil(W / 64.0) * 64)
-        rgb = NHWC(F, Hp, Wp, 8, dt, dev)
         offsets = torch.zeros(P, 2, H, W, dtype=torch.float32, device=dev)
         om = NHWC(F, H, W, 8, dt, dev)
-        plan.add('pack_burst', lib.dbsr_pack_burst, B, N, H, W, bufs['burst'].data_ptr(), raw.d(0), Hp, Wp, rgb.d(0))
-        flow_out = NHWC(P, Hp // 4, Wp // 4, 2, torch.float32, dev)
-        self.pwc.build(plan, dt, dev, F, Hp, Wp, P, first_map=(N - 1, N, 0, 0), second_map=(N - 1, N, 1, 1), rgb=rgb,
-                       flow_out=flow_out)
-        plan.add('flow_finalize', lib.dbsr_flow_finalize, B, N, Hp // 4, Wp // 4, flow_out.d(0), H, W, Hp, Wp,
-                 offsets.data_ptr(), self.offset_modulo, om.d(0))
+        if ext_flow:
+            # the caller's offsets: no PWC-Net ops (and no RGB frames for it); `offsets` is a copy, `om` as
+            # dbsr_flow_finalize writes it
+            if P == 0:
+                raise ValueError('DBSRTrainer: external flows need a burst of at least two frames')
+            rgb = flow_out = None
+            bufs['flow'] = torch.zeros(P, 2, H, W, dtype=torch.float32, device=dev)
+            plan.add('pack_burst', lib.dbsr_pack_burst, B, N, H, W, bufs['burst'].data_ptr(), raw.d(0), Hp, Wp,
+                     L.NULL_TENSOR)
+            plan.add('offsets_export', lib.dbsr_offsets_export, B, N, H, W, bufs['flow'].data_ptr(), 2 * H * W,
+                     offsets.data_ptr(), self.offset_modulo, om.d(0))
+        else:
+            rgb = NHWC(F, Hp, Wp, 8, dt, dev)
+            plan.add('pack_burst', lib.dbsr_pack_burst, B, N, H, W, bufs['burst'].data_ptr(), raw.d(0), Hp, Wp,
+                     rgb.d(0))
+            flow_out = NHWC(P, Hp // 4, Wp // 4, 2, torch.float32, dev)
+            self.pwc.build(plan, dt, dev, F, Hp, Wp, P, first_map=(N - 1, N, 0, 0), second_map=(N - 1, N, 1, 1),
+                           rgb=rgb, flow_out=flow_out)
+            plan.add('flow_finalize', lib.dbsr_flow_finalize, B, N, Hp // 4, Wp // 4, flow_out.d(0), H, W, Hp, Wp,
+                     offsets.data_ptr(), self.offset_modulo, om.d(0))
 
         def res_fwd(name, blocks, n, hw_, x, xc0, width, last_out=None):
             """ResBlocks with every activation kept: returns [(x, xc0, t, y, yc0)] per block."""
@@ -474,8 +497,9 @@ class DBSRTrainer:
         dWP = NHWC(F, H, W, 2 * pd + od, dt, dev)
         plan.conv('bwd.wp.init.bd', self.wp_init_bd, F, gq0, 0, hw, dWP, 0, L.ACT_NONE)
         plan.conv('bwd.wp.init.of', self.wp_init_of, F, gq0, 0, hw, dWP, 2 * pd, L.ACT_NONE, gate=WP, gc0=2 * pd)
-        # offset-feature extractor (its input, offsets % 1 from the frozen PWC-Net, takes no gradient)
-        go, _ = res_bwd('ofe.res', self.ofe_res, ofe_s, F, hw, dWP, 2 * pd, gate_first=True)
+        # offset-feature extractor (the gradient that reaches its input, offsets % modulo, is taken below with
+        # flow_grad; without it the offsets are a constant)
+        go, go_c0 = res_bwd('ofe.res', self.ofe_res, ofe_s, F, hw, dWP, 2 * pd, gate_first=True)
         wgrad('ofe.init', self.ofe_init, F, H, W, om, 0, go, 0)
         # merge prep + projection
         dPJ = NHWC(F, H, W, r8(pd), dt, dev)
@@ -496,6 +520,18 @@ class DBSRTrainer:
             need = lib.dbsr_warp_backward_gather_workspace_bytes(P, H, W)
             plan.add('bwd.warp', lib.dbsr_warp_backward_gather, P, H, W, C, dWf.d(0), offsets.data_ptr(), 2 * H * W,
                      E.d(0, (N - 1, N, 1, 1)), dE.d(0, (N - 1, N, 1, 1)), ws('wb', need), need)
+        plan.dflow = None
+        if flow_grad and P > 0:
+            # dL/d(offsets), fp32 [P][2][H][W]: the offset-feature extractor's first conv back to its 2-channel
+            # input for the frames n >= 1 (go is gated; the modulo has derivative 1; the reference frame's offsets
+            # are a constant) written by the dgrad conv's fp32 NCHW epilogue, then the warp's flow gradient added
+            plan.dflow = torch.zeros(P, 2, H, W, dtype=torch.float32, device=dev)
+            ddesc = L.tensor_desc(plan.dflow, 1, 0, img_stride=2 * H * W, dtype=torch.float32)
+            plan.conv('bwd.ofe.init.dgrad', self.ofe_init.bwd, P, go, go_c0, hw, None, 0, L.ACT_NONE,
+                      xmap=(N - 1, N, 1, 1), out_mode=L.OUT_NCHW_F32, y_desc=ddesc)
+            plan.add('bwd.warp.flow', lib.dbsr_warp_flow_backward, P, H, W, C, E.d(0, (N - 1, N, 1, 1)), dWf.d(0),
+                     offsets.data_ptr(), 2 * H * W, plan.dflow.data_ptr(), 2 * H * W, 1,
+                     work=('byte', float(P) * H * W * C * dWf.t.element_size() * 5))
         plan.add('bwd.enc.gate', lib.dbsr_gate_copy, B, H * W, C, dEref.d(0), E.d(0, (1, N, 0, 1)),
                  dE.d(0, (1, N, 0, 1)))
         # encoder
@@ -526,16 +562,10 @@ class DBSRTrainer:
         return plan
 
     # ------------------------------------------------------------------------------------------------
-    def step(self, burst, frame_gt):
-        """One training step on this rank's bursts [B,N,4,H,W] and ground truth [B,3,sH,sW]; returns the
-        rank-local loss (device tensor, shape [1])."""
-        B, N, _, H, W = burst.shape
-        key = (B, N, H, W)
-        plan = self.plans.get(key)
-        if plan is None:
-            plan = self.plans[key] = self._build(B, N, H, W)
-        plan.bufs['burst'].copy_(burst.to(torch.float32), non_blocking=True)
-        plan.bufs['gt'].copy_(frame_gt.to(torch.float32), non_blocking=True)
+    def step(self, burst, frame_gt, flow=None):
+        """One training step on this rank's bursts [B,N,4,H,W] and ground truth [B,3,sH,sW] (flow: the caller's
+        offsets [B,N-1,2,H,W] instead of PWC-Net's); returns the rank-local loss (device tensor, shape [1])."""
+        plan = self._load(burst, frame_gt, flow)
         stream = L.stream_ptr(self.dev)
         # segments of the op list between the gradient buckets' completion points: each segment is one HIP
         # graph replay (after one eager step), and a bucket's all-reduce is issued right after its segment
@@ -569,6 +599,7 @@ class DBSRTrainer:
     def _optimizer_step(self, stream):
         self.step_count += 1
         lib = L.lib()
+        self._unscale_flow_grad(stream)
         if self.scaling:
             # Order (step() calls this after every bucket's all-reduce has completed, before anything else touches
             # the gradients): unscale + overflow check on the SUMMED gradients, then the guarded Adam, then the
@@ -593,24 +624,52 @@ class DBSRTrainer:
         if eng is not None:
             eng.weights_stale = True
 
-    def forward_backward(self, burst, frame_gt):
+    def forward_backward(self, burst, frame_gt, flow=None):
         """Loss and gradients only (no all-reduce, no optimizer step): for tests."""
-        B, N, _, H, W = burst.shape
-        key = (B, N, H, W)
-        plan = self.plans.get(key)
-        if plan is None:
-            plan = self.plans[key] = self._build(B, N, H, W)
-        plan.bufs['burst'].copy_(burst.to(torch.float32), non_blocking=True)
-        plan.bufs['gt'].copy_(frame_gt.to(torch.float32), non_blocking=True)
+        plan = self._load(burst, frame_gt, flow)
         plan.run(L.stream_ptr(self.dev))
         self._unscale_only(L.stream_ptr(self.dev))
         return self.loss, plan.bufs['pred']
+
+    def _load(self, burst, frame_gt, flow=None, flow_grad=None):
+        """The plan of this burst shape (the PWC-Net plan, or with `flow` the external-flow plan) with its inputs
+        copied in."""
+        plan = self._plan(burst.shape, flow, flow_grad)
+        plan.bufs['burst'].copy_(burst.to(torch.float32), non_blocking=True)
+        if frame_gt is not None:
+            plan.bufs['gt'].copy_(frame_gt.to(torch.float32), non_blocking=True)
+        if flow is not None:
+            plan.bufs['flow'].copy_(flow.detach().to(torch.float32).reshape(plan.bufs['flow'].shape),
+                                    non_blocking=True)
+        self._flow_plan = plan
+        return plan
+
+    def flow_grad(self):
+        """dL/d(offsets) of the last backward, fp32 [B,N-1,2,H,W] (a view of the plan's buffer, overwritten by the
+        next backward of the same plan; unscaled when a loss scaler runs).  Needs flow_grad=True."""
+        plan = self._flow_plan
+        if plan is None or plan.dflow is None:
+            raise RuntimeError('DBSRTrainer.flow_grad(): build the trainer with flow_grad=True and run a backward '
+                               '(a burst of at least two frames)')
+        B, N = plan.bufs['burst'].shape[:2]
+        return plan.dflow.view(B, N - 1, *plan.dflow.shape[1:])
+
+    def _unscale_flow_grad(self, stream):
+        """With a loss scaler the backward ran on the scaled loss: divide dL/d(offsets) by the scale on the device
+        (dbsr_grad_unscale_check, which also raises found_inf on an overflow); nothing is read back.  Whatever
+        non-finite value reaches this rank-local buffer also reaches a parameter gradient (dWf feeds bwd.warp, go
+        feeds wgrad.ofe.init), which the all-reduce carries to every rank: the ranks still decide alike."""
+        plan = self._flow_plan
+        if self.scaling and plan is not None and plan.dflow is not None:
+            L.check(L.lib().dbsr_grad_unscale_check(plan.dflow.numel(), plan.dflow.data_ptr(), self._ls.data_ptr(),
+                                                    stream), 'grad_unscale_check')
 
     def _unscale_only(self, stream):
         """forward_backward with a scaler: grads() are the true (unscaled) gradients; the overflow flag goes to
         found_inf() and is cleared here, since no dbsr_loss_scale_update follows (the state is a step's alone)."""
         if not self.scaling:
             return
+        self._unscale_flow_grad(stream)
         L.check(L.lib().dbsr_grad_unscale_check(self.n_params, self.flat_grad.data_ptr(), self._ls.data_ptr(),
                                                 stream), 'grad_unscale_check')
         flag = self._ls[L.LS_FOUND_INF:L.LS_FOUND_INF + 1]
@@ -638,20 +697,25 @@ class DBSRTrainer:
 
     # ---- autograd through DBSRNet.forward (the reference's own loop: pred, _ = net(burst); objective(pred,
     # gt).backward(); optimizer.step(); actors/dbsr_actors.py:27-47, trainers/simple_trainer.py:78-81) ----
-    def _plan(self, shape):
+    def _plan(self, shape, flow=None, flow_grad=None):
+        """The plan of a burst shape; with external flows a plan of its own (no PWC-Net ops), keyed separately.
+        flow_grad: None = the trainer's setting (the autograd path asks per call, by flow.requires_grad)."""
         B, N, _, H, W = shape
-        key = (B, N, H, W)
+        if flow is not None and tuple(flow.shape) != (B, N - 1, 2, H, W):
+            raise ValueError('DBSRTrainer: flow must be [B,N-1,2,H,W] = %s, got %s'
+                             % ((B, N - 1, 2, H, W), tuple(flow.shape)))
+        fg = self.want_flow_grad if flow_grad is None else bool(flow_grad)
+        key = (B, N, H, W) if flow is None else (B, N, H, W, 'flow') + ((fg,) if fg != self.want_flow_grad else ())
         plan = self.plans.get(key)
         if plan is None:
-            plan = self.plans[key] = self._build(B, N, H, W)
+            plan = self.plans[key] = self._build(B, N, H, W, ext_flow=flow is not None, flow_grad=fg)
         return plan
 
-    def forward_saved(self, burst):
+    def forward_saved(self, burst, flow=None, flow_grad=None):
         """The training forward with every activation kept in the plan's buffers: (pred, offsets, fusion
         weights, token).  The activations stay valid until the next forward of the same shape; `token`
-        names them for backward_from."""
-        plan = self._plan(burst.shape)
-        plan.bufs['burst'].copy_(burst.to(torch.float32), non_blocking=True)
+        names them for backward_from.  flow: the caller's offsets [B,N-1,2,H,W] instead of PWC-Net's."""
+        plan = self._load(burst, None, flow, flow_grad)
         plan.run_list(plan.ops[:plan.fwd_end], L.stream_ptr(self.dev))
         plan.gen += 1
         B, N, _, H, W = burst.shape
@@ -670,6 +734,7 @@ class DBSRTrainer:
         fn, args, name, _ = plan.grad_in_op
         L.check(fn(*args, L.stream_ptr(self.dev)), name)
         plan.run_list(plan.ops[plan.fwd_end + 1:], L.stream_ptr(self.dev))
+        self._flow_plan = plan
         return [self.flat_grad[o:o + k].view(p.shape).clone() for p in self.params for (o, k) in [self.offset[id(p)]]]
 
     def grads(self):
@@ -747,16 +812,10 @@ class DBSRRealWorldTrainer(DBSRTrainer):
         psnr = [-10.0 * math.log10(sq / (3.0 * n + 1e-12)) for sq, n in st.tolist() if sq > 0.0 and n > 0.0]
         return {'loss': float(self._loss2[0]), 'psnr': sum(psnr) / len(psnr) if psnr else 0}
 
-    def _load(self, burst, frame_gt):
-        plan = self._plan(burst.shape)
-        plan.bufs['burst'].copy_(burst.to(torch.float32), non_blocking=True)
-        plan.bufs['gt'].copy_(frame_gt.to(torch.float32), non_blocking=True)
-        return plan
-
-    def step(self, burst, frame_gt):
-        """One fine-tuning step on this rank's bursts [B,N,4,H,W] and ground truth [B,3,8H,8W]; returns the
-        rank-local loss (device tensor, shape [1])."""
-        plan = self._load(burst, frame_gt)
+    def step(self, burst, frame_gt, flow=None):
+        """One fine-tuning step on this rank's bursts [B,N,4,H,W] and ground truth [B,3,8H,8W] (flow: as
+        DBSRTrainer.step); returns the rank-local loss (device tensor, shape [1])."""
+        plan = self._load(burst, frame_gt, flow)
         stream = L.stream_ptr(self.dev)
         fe = plan.fwd_end
         # the forward, [the objective, eager], then the backward cut at the gradient buckets' completion points;
@@ -790,9 +849,9 @@ class DBSRRealWorldTrainer(DBSRTrainer):
         self._optimizer_step(stream)
         return self.loss.clone()
 
-    def forward_backward(self, burst, frame_gt):
+    def forward_backward(self, burst, frame_gt, flow=None):
         """Loss and gradients only (no all-reduce, no optimizer step): for tests."""
-        plan = self._load(burst, frame_gt)
+        plan = self._load(burst, frame_gt, flow)
         stream = L.stream_ptr(self.dev)
         plan.run_list(plan.ops[:plan.fwd_end], stream)
         self._objective(plan, stream)
@@ -852,11 +911,13 @@ def allreduce_bucket(flat_grad, lo, hi, group=None):
 
 class _DBSRTrainForward(torch.autograd.Function):
     """DBSRNet.forward under autograd: the HIP training forward (activations saved) and, on backward, the
-    HIP backward from dL/dpred into the DBSR parameters' gradients (PWC-Net is frozen, encoders.py:56-61)."""
+    HIP backward from dL/dpred into the DBSR parameters' gradients (PWC-Net is frozen, encoders.py:56-61) and,
+    with the caller's own `flow`, into that flow (through the warp and the offset-feature extractor)."""
 
     @staticmethod
-    def forward(ctx, burst, engine, *params):
-        pred, offs, fw, token = engine.forward_saved(burst)
+    def forward(ctx, burst, engine, flow, *params):
+        ctx.flow_grad = flow is not None and flow.requires_grad
+        pred, offs, fw, token = engine.forward_saved(burst, flow, ctx.flow_grad if flow is not None else None)
         ctx.engine, ctx.token = engine, token
         ctx.mark_non_differentiable(offs, fw)
         return pred, offs, fw
@@ -864,8 +925,10 @@ class _DBSRTrainForward(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gpred, goffs, gfw):
         if gpred is None:
-            return (None, None) + tuple(None for _ in ctx.engine.params)
-        return (None, None) + tuple(ctx.engine.backward_from(ctx.token, gpred.contiguous()))
+            return (None, None, None) + tuple(None for _ in ctx.engine.params)
+        grads = tuple(ctx.engine.backward_from(ctx.token, gpred.contiguous()))
+        gflow = ctx.engine.flow_grad().clone() if ctx.flow_grad else None
+        return (None, None, gflow) + grads
 
 
 def _aliased(eng):
@@ -879,11 +942,12 @@ def _aliased(eng):
                p.dtype == torch.float32 for p in eng.params)
 
 
-def train_forward(net, burst):
-    """pred, {'offsets', 'fusion_weights'} of DBSRNet.forward with autograd to the DBSR parameters."""
+def train_forward(net, burst, flow=None):
+    """pred, {'offsets', 'fusion_weights'} of DBSRNet.forward with autograd to the DBSR parameters and, when the
+    caller supplies the offsets (flow [B,N-1,2,H,W], e.g. their own alignment network's output), to that flow."""
     eng = getattr(net, '_train_engine', None)
     if eng is None or eng.net is not net or eng.dtype != net.compute_dtype or not _aliased(eng):
         eng = net._train_engine = DBSRTrainer(net, optimizer=False)
-    pred, offs, fw = _DBSRTrainForward.apply(burst, eng, *eng.params)
+    pred, offs, fw = _DBSRTrainForward.apply(burst, eng, flow, *eng.params)
     from .engine import DBSRAux
     return pred, DBSRAux(offs, fw)

@@ -585,6 +585,33 @@ size_t dbsr_warp_backward_gather_workspace_bytes(int n, int h, int w);
 int dbsr_warp_backward_gather(int n, int h, int w, int c, dbsr_tensor dout, const float* flow,
                               long long flow_img_stride, dbsr_tensor gate, dbsr_tensor dfeat, void* workspace,
                               size_t workspace_bytes, void* stream);
+/* ---------------- flow gradients (csrc/flow_grad.hip; exports added under ABI 23) ----------------
+ * warp backward w.r.t. the flow (warp.py:19-46 under autograd; grid_sample's zero-padding backward w.r.t. the
+ * grid, align_corners=False): with dbsr_warp_bilinear's sample position, corners v00..v11 (0 outside the image) and
+ * weights,
+ *   dflow[p][0][y][x] = sum_c dout[p,c] * (wy0 * (v01 - v00) + wy1 * (v11 - v10))
+ *   dflow[p][1][y][x] = sum_c dout[p,c] * (wx0 * (v10 - v00) + wx1 * (v11 - v01))
+ * feat (with its frame map) and flow exactly as the forward takes them; dout NHWC of feat's dtype (f32 / bf16 /
+ * f16); c, ld, c0 multiples of 8.  dflow is fp32 [n][2][h][w], images dflow_img_stride floats apart, written whole
+ * (accumulate 0) or added to (accumulate != 0).  Each pixel owns its two results: no atomics, deterministic. */
+int dbsr_warp_flow_backward(int n, int h, int w, int c, dbsr_tensor feat, dbsr_tensor dout, const float* flow,
+                            long long flow_img_stride, float* dflow, long long dflow_img_stride, int accumulate,
+                            void* stream);
+/* dbsr_backwarp's backward (pwcnet.py:16-38; in, flow, scale as the forward, dout of in's dtype).  The mask is
+ * thresholded in place by the reference and carries no gradient:
+ *   din   = bilinear transpose of mask * dout           (fp32 NHWC, c channels; zeroed here, then fp32 atomics:
+ *                                                        equal run to run up to fp32 summation order)
+ *   dflow = mask * scale * {W/(W-1), H/(H-1)} * sum_c dout * d(sample)/d{ix, iy}   (fp32 NHWC, 2 channels;
+ *                                                        owner-computes, deterministic)
+ * din.ptr or dflow.ptr NULL: that gradient is not wanted (not both; `in` is read only for dflow). */
+int dbsr_backwarp_backward(int n, int h, int w, int c, dbsr_tensor in, dbsr_tensor flow, float scale,
+                           dbsr_tensor dout, dbsr_tensor din, dbsr_tensor dflow, void* stream);
+/* Caller-supplied full-resolution offsets into the training forward: flow [B*(N-1)][2][H][W] fp32 (images
+ * flow_img_stride floats apart) -> offsets (the same layout, contiguous; may be NULL) and offs_mod channels
+ * [c0, c0+2) of the B*N frames = offsets % modulo (modulo 0: no remainder), zeros for each burst's reference
+ * frame (merging.py:98-105): what dbsr_flow_finalize writes from PWC-Net's quarter-resolution flow. */
+int dbsr_offsets_export(int B, int N, int H, int W, const float* flow, long long flow_img_stride, float* offsets,
+                        float modulo, dbsr_tensor offs_mod, void* stream);
 /* out = [gate > 0] * in over n NHWC images of c channels (c, ld, c0 multiples of 8). */
 int dbsr_gate_copy(int n, int hw, int c, dbsr_tensor in, dbsr_tensor gate, dbsr_tensor out, void* stream);
 /* torch.optim.Adam step (weight_decay 0) on flat fp32 buffers; grad is scaled by grad_scale first. */
