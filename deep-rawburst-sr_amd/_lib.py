@@ -182,6 +182,16 @@ def lib():
                                         c_float, c_float, c_void_p, c_void_p], c_int),
             'dbsr_loss_scale_update': ([c_void_p, c_float, c_float, c_int, c_void_p], c_int),
             'dbsr_dgrad_weights': ([c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p], c_int),
+            'dbsr_conv_wgrad_sd_workspace_bytes': ([c_int, c_int, c_int, c_int, c_int, c_int], c_size_t),
+            'dbsr_conv_wgrad_sd': ([c_int, c_int, c_int, Tensor, c_int, c_int, c_int, Tensor, c_int, c_int, c_int, c_int,
+                                    c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p], c_int),
+            'dbsr_dgrad_sd_packed_elems': ([c_int, c_int, c_int], c_size_t),
+            'dbsr_dgrad_sd_pack': ([c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p], c_int),
+            'dbsr_conv_dgrad_sd': ([c_int, c_int, c_int, Tensor, c_int, c_int, c_int, Tensor, c_int, c_int, c_int, c_int,
+                                    c_int, c_void_p, c_void_p], c_int),
+            'dbsr_act_backward': ([c_int, c_int, c_int, c_int, Tensor, Tensor, Tensor, c_void_p], c_int),
+            'dbsr_flow_finalize_backward': ([c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, Tensor,
+                                             c_void_p], c_int),
             'dbsr_pwc_dense': ([c_int, c_int, c_int, Tensor, c_int, c_void_p, Tensor, c_void_p], c_int),
             'dbsr_pwc_dense_supported': ([c_int, c_int, c_int], c_int),
             'dbsr_pwc_refine': ([c_int, c_int, c_int, Tensor, c_void_p, Tensor, Tensor, c_void_p], c_int),
@@ -237,6 +247,8 @@ EXPORTED = ['dbsr_abi_version', 'dbsr_last_error', 'dbsr_conv_packed_elems', 'db
             'dbsr_warp_backward_gather_workspace_bytes', 'dbsr_warp_backward_gather', 'dbsr_gate_copy',
             'dbsr_warp_flow_backward', 'dbsr_backwarp_backward', 'dbsr_offsets_export',
             'dbsr_adam_step', 'dbsr_dgrad_weights',
+            'dbsr_conv_wgrad_sd_workspace_bytes', 'dbsr_conv_wgrad_sd', 'dbsr_dgrad_sd_packed_elems',
+            'dbsr_dgrad_sd_pack', 'dbsr_conv_dgrad_sd', 'dbsr_act_backward', 'dbsr_flow_finalize_backward',
             'dbsr_l1_loss_backward_scaled', 'dbsr_grad_unscale_check', 'dbsr_adam_step_guarded',
             'dbsr_loss_scale_update',
             'dbsr_resize_bilinear', 'dbsr_gauss_reflect', 'dbsr_color_fit', 'dbsr_color_apply', 'dbsr_pwc_dense',

@@ -15,7 +15,11 @@
 //   dbsr::fuse_backward(weights, feats, fused, dfused)
 //   dbsr::conv2d_fused(x, w, b, stride, padding, dilation, act, residual, post_act)
 //                                                  nn.Conv2d + models/layers/blocks.py:46-96 epilogues
-// Autograd formulas for correlation / backwarp / warp / fusion are registered from Python (dbsr_amd/torch_ops.py)
+//   dbsr::conv2d_backward(grad, x, w, out, stride, padding, dilation, act, need_x, need_w, need_b)
+//   dbsr::conv_transpose2d_k4s2(x, w, b) / _backward   nn.ConvTranspose2d(k4, s2, p1), pwcnet.py:119-120
+//   dbsr::flow_finalize(flow, H, W) / _backward    pwcnet.py:274-279
+//   dbsr::resize_bilinear(x, Hp, Wp)               pwcnet.py:266-271 (forward only)
+// Autograd formulas for correlation / backwarp / warp / fusion / the convs are registered from Python (dbsr_amd/torch_ops.py)
 // with torch.library.register_autograd on top of the *_backward ops.
 #include <ATen/ATen.h>
 #include <ATen/hip/HIPContext.h>
@@ -357,9 +361,245 @@ at::Tensor conv2d_fused(const at::Tensor& x, const at::Tensor& weight, const c10
     return nchw(y, Cout);
 }
 
+// ------------------------------------------------------------------------------------------------
+// PWC-Net training (csrc/pwc_grad.hip): the backward of conv2d_fused (act none / ReLU / LeakyReLU, no residual),
+// ConvTranspose2d(k4, s2, p1) and the flow's final resize, forward and backward.
+// ------------------------------------------------------------------------------------------------
+at::Tensor f32_scratch(size_t bytes, const at::Tensor& like) {
+    return at::empty({(int64_t)std::max<size_t>((bytes + 3) / 4, 4)}, like.options().dtype(at::kFloat));
+}
+
+// a plain dbsr_conv2d of NHWC `xs` (ld = conv_ld(cin)) with torch-layout fp32 weights, no bias / activation
+at::Tensor run_conv(const at::Tensor& xs, int64_t N, int64_t H, int64_t W, int64_t cin, const at::Tensor& w32,
+                    int64_t cout, int64_t k, int64_t stride, int64_t pad, int64_t dil, int64_t oh, int64_t ow) {
+    void* s = cur_stream();
+    auto wp = at::empty({(int64_t)dbsr_conv_packed_elems(cout, cin, k, k)}, xs.options());
+    check(dbsr_conv_pack_weights(w32.data_ptr<float>(), nullptr, cout, cin, k, k, dcode(xs.scalar_type()), 1,
+                                 wp.data_ptr(), nullptr, s),
+          "dbsr_conv_pack_weights");
+    auto y = at::zeros({N, oh, ow, r8(cout)}, xs.options());
+    dbsr_conv_desc d{};
+    d.n_frames = N;
+    d.x = desc(xs, conv_ld(cin));
+    d.in_h = H; d.in_w = W; d.cin = cin;
+    d.w = wp.data_ptr();
+    d.bias = nullptr;
+    d.cout = cout; d.kh = k; d.kw = k; d.stride = stride; d.pad = pad; d.dil = dil;
+    d.y = desc(y, r8(cout));
+    d.out_h = oh; d.out_w = ow;
+    d.act = DBSR_ACT_NONE;
+    d.res = null_desc();
+    d.gate = null_desc();
+    d.out_mode = DBSR_OUT_NHWC;
+    const size_t need = dbsr_conv_workspace_bytes(&d);
+    auto ws = at::zeros({(int64_t)std::max<size_t>(need / 4, 1)}, xs.options().dtype(at::kFloat));
+    d.workspace = ws.data_ptr();
+    d.workspace_bytes = need;
+    check(dbsr_conv2d(&d, s), "dbsr_conv2d");
+    return y;
+}
+
+at::Tensor chan_sum(const at::Tensor& t, int64_t N, int64_t hw, int64_t C, int64_t ld) {
+    auto out = at::empty({C}, t.options().dtype(at::kFloat));
+    const size_t need = dbsr_chan_sum_workspace_bytes(N, hw, C);
+    auto ws = f32_scratch(need, t);
+    check(dbsr_chan_sum(N, hw, C, desc(t, ld), out.data_ptr<float>(), 0, ws.data_ptr(), need, cur_stream()),
+          "dbsr_chan_sum");
+    return out;
+}
+
+// (an unwanted gradient is returned as an empty tensor and is not computed)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> conv2d_backward(const at::Tensor& grad, const at::Tensor& x,
+                                                               const at::Tensor& weight, const at::Tensor& out,
+                                                               int64_t stride, int64_t padding, int64_t dilation,
+                                                               int64_t act, bool need_x, bool need_w, bool need_b) {
+    need_hip(grad, "conv2d_backward");
+    need_hip(x, "conv2d_backward");
+    need_hip(weight, "conv2d_backward");
+    TORCH_CHECK(x.dim() == 4 && weight.dim() == 4 && grad.dim() == 4 && weight.size(1) == x.size(1) &&
+                weight.size(2) == weight.size(3) && grad.size(0) == x.size(0) && grad.size(1) == weight.size(0),
+                "dbsr::conv2d_backward: shapes");
+    TORCH_CHECK(act == DBSR_ACT_NONE || act == DBSR_ACT_RELU || act == DBSR_ACT_LRELU, "dbsr::conv2d_backward: act");
+    const auto dt = x.scalar_type();
+    const int dc = dcode(dt);
+    const int64_t N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+    const int64_t Cout = weight.size(0), k = weight.size(2), oh = grad.size(2), ow = grad.size(3);
+    at::Tensor dx = at::empty({0}, x.options()), dw = at::empty({0}, weight.options()),
+               db = at::empty({0}, weight.options());
+    if (!need_x && !need_w && !need_b) return {dx, dw, db};
+    void* s = cur_stream();
+    const int64_t ldc = conv_ld(Cout);
+    auto dpre = nhwc(grad, ldc, dt);
+    if (act != DBSR_ACT_NONE) {
+        need_hip(out, "conv2d_backward");
+        TORCH_CHECK(out.sizes() == grad.sizes(), "dbsr::conv2d_backward: out must be the forward's output");
+        auto o = nhwc(out, ldc, dt), g = dpre;
+        dpre = at::zeros_like(g);
+        check(dbsr_act_backward(N, oh * ow, Cout, act, desc(g, ldc), desc(o, ldc), desc(dpre, ldc), s),
+              "dbsr_act_backward");
+    }
+    if (need_w) {
+        auto xs = nhwc(x, r8(Cin), dt);
+        auto dw32 = at::empty({Cout, Cin, k, k}, x.options().dtype(at::kFloat));
+        at::Tensor db32;
+        if (need_b) db32 = at::empty({Cout}, x.options().dtype(at::kFloat));
+        float* dbp = need_b ? db32.data_ptr<float>() : nullptr;
+        if ((k == 1 || k == 3) && stride == 1 && dilation == 1 && padding == k / 2) {
+            const size_t need = dbsr_conv_wgrad_workspace_bytes(N, H, W, Cin, Cout, k);
+            auto ws = f32_scratch(need, x);
+            check(dbsr_conv_wgrad_bias(N, H, W, desc(xs, r8(Cin)), Cin, desc(dpre, ldc), Cout, k, dw32.data_ptr<float>(),
+                                       dbp, 0, ws.data_ptr(), need, s),
+                  "dbsr_conv_wgrad_bias");
+        } else {
+            const size_t need = dbsr_conv_wgrad_sd_workspace_bytes(N, oh, ow, Cin, Cout, k);
+            auto ws = f32_scratch(need, x);
+            check(dbsr_conv_wgrad_sd(N, H, W, desc(xs, r8(Cin)), Cin, oh, ow, desc(dpre, ldc), Cout, k, stride, dilation,
+                                     padding, dw32.data_ptr<float>(), dbp, 0, ws.data_ptr(), need, s),
+                  "dbsr_conv_wgrad_sd");
+        }
+        dw = dw32.to(weight.scalar_type());
+        if (need_b) db = db32.to(weight.scalar_type());
+    } else if (need_b) {
+        db = chan_sum(dpre, N, oh * ow, Cout, ldc).to(weight.scalar_type());
+    }
+    if (need_x) {
+        auto w32 = weight.to(at::kFloat).contiguous();
+        const int64_t padt = dilation * (k - 1) - padding;
+        if (stride == 1 && padt >= 0) {
+            // the stride-1 route: the forward conv over dpre with dbsr_dgrad_weights
+            auto wt = at::empty({Cin, Cout, k, k}, w32.options());
+            check(dbsr_dgrad_weights(w32.data_ptr<float>(), Cout, Cin, k, k, wt.data_ptr<float>(), s),
+                  "dbsr_dgrad_weights");
+            dx = nchw(run_conv(dpre, N, oh, ow, Cout, wt, Cin, k, 1, padt, dilation, H, W), Cin);
+        } else {
+            auto wp = at::empty({(int64_t)dbsr_dgrad_sd_packed_elems(Cout, Cin, k)}, x.options());
+            check(dbsr_dgrad_sd_pack(w32.data_ptr<float>(), Cout, Cin, k, dc, wp.data_ptr(), s), "dbsr_dgrad_sd_pack");
+            auto y = at::empty({N, H, W, r8(Cin)}, x.options());
+            check(dbsr_conv_dgrad_sd(N, H, W, desc(y, r8(Cin)), Cin, oh, ow, desc(dpre, ldc), Cout, k, stride, dilation,
+                                     padding, wp.data_ptr(), s),
+                  "dbsr_conv_dgrad_sd");
+            dx = nchw(y, Cin);
+        }
+    }
+    return {dx, dw, db};
+}
+
+// nn.ConvTranspose2d(cin -> cout <= 4, k 4, s 2, p 1): weight torch's [cin][cout][4][4]
+at::Tensor conv_transpose2d_k4s2(const at::Tensor& x, const at::Tensor& weight, const c10::optional<at::Tensor>& bias) {
+    need_hip(x, "conv_transpose2d_k4s2");
+    need_hip(weight, "conv_transpose2d_k4s2");
+    TORCH_CHECK(x.dim() == 4 && weight.dim() == 4 && weight.size(0) == x.size(1) && weight.size(2) == 4 &&
+                weight.size(3) == 4 && weight.size(1) >= 1 && weight.size(1) <= 4,
+                "dbsr::conv_transpose2d_k4s2: x [N,Cin,H,W], weight [Cin,Cout<=4,4,4]");
+    const auto dt = x.scalar_type();
+    const int64_t N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3), Cout = weight.size(1);
+    const bool has_b = bias.has_value() && bias->defined();
+    if (has_b) {
+        need_hip(*bias, "conv_transpose2d_k4s2");
+        TORCH_CHECK(bias->dim() == 1 && bias->size(0) == Cout, "dbsr::conv_transpose2d_k4s2: bias must be [Cout]");
+    }
+    auto xs = nhwc(x, r8(Cin), dt);
+    // [ky][kx][cout][cin8] fp32, channels zero-padded
+    auto wr = at::zeros({4, 4, Cout, r8(Cin)}, x.options().dtype(at::kFloat));
+    wr.narrow(3, 0, Cin).copy_(weight.to(at::kFloat).permute({2, 3, 1, 0}));
+    auto b32 = has_b ? bias->to(at::kFloat).contiguous() : at::zeros({Cout}, x.options().dtype(at::kFloat));
+    auto out = at::empty({N, 2 * H, 2 * W, Cout}, x.options().dtype(at::kFloat));
+    check(dbsr_conv_transpose_k4s2(N, H, W, Cin, Cout, desc(xs, r8(Cin)), wr.data_ptr<float>(), b32.data_ptr<float>(),
+                                   desc(out, Cout), cur_stream()),
+          "dbsr_conv_transpose_k4s2");
+    return out.permute({0, 3, 1, 2}).contiguous().to(dt);
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> conv_transpose2d_k4s2_backward(const at::Tensor& grad, const at::Tensor& x,
+                                                                              const at::Tensor& weight, bool need_x,
+                                                                              bool need_w, bool need_b) {
+    need_hip(grad, "conv_transpose2d_k4s2_backward");
+    need_hip(x, "conv_transpose2d_k4s2_backward");
+    need_hip(weight, "conv_transpose2d_k4s2_backward");
+    TORCH_CHECK(x.dim() == 4 && weight.dim() == 4 && grad.dim() == 4 && weight.size(0) == x.size(1) &&
+                weight.size(2) == 4 && weight.size(3) == 4 && grad.size(1) == weight.size(1) &&
+                grad.size(2) == 2 * x.size(2) && grad.size(3) == 2 * x.size(3),
+                "dbsr::conv_transpose2d_k4s2_backward: shapes");
+    const auto dt = x.scalar_type();
+    const int64_t N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3), Cout = weight.size(1);
+    at::Tensor dx = at::empty({0}, x.options()), dw = at::empty({0}, weight.options()),
+               db = at::empty({0}, weight.options());
+    if (!need_x && !need_w && !need_b) return {dx, dw, db};
+    void* s = cur_stream();
+    const int64_t ldg = conv_ld(Cout);
+    auto g = nhwc(grad, ldg, dt);
+    if (need_x) {
+        // a k4 s2 p1 conv over dy whose weights are the transposed conv's as they are: [Cin][Cout][4][4]
+        auto w32 = weight.to(at::kFloat).contiguous();
+        dx = nchw(run_conv(g, N, 2 * H, 2 * W, Cout, w32, Cin, 4, 2, 1, 1, H, W), Cin);
+    }
+    if (need_w) {
+        // the roles swapped: "input" = dy (2H x 2W, Cout channels), "output gradient" = x (H x W, Cin channels)
+        auto xs = nhwc(x, r8(Cin), dt);
+        auto dw32 = at::empty({Cin, Cout, 4, 4}, x.options().dtype(at::kFloat));
+        const size_t need = dbsr_conv_wgrad_sd_workspace_bytes(N, H, W, Cout, Cin, 4);
+        auto ws = f32_scratch(need, x);
+        check(dbsr_conv_wgrad_sd(N, 2 * H, 2 * W, desc(g, ldg), Cout, H, W, desc(xs, r8(Cin)), Cin, 4, 2, 1, 1,
+                                 dw32.data_ptr<float>(), nullptr, 0, ws.data_ptr(), need, s),
+              "dbsr_conv_wgrad_sd");
+        dw = dw32.to(weight.scalar_type());
+    }
+    if (need_b) db = chan_sum(g, N, 4 * H * W, Cout, ldg).to(weight.scalar_type());
+    return {dx, dw, db};
+}
+
+// pwcnet.py:274-279: 20 * bilinear(flow -> H x W) * (W / Wp, H / Hp); Hp / Wp 0: four times the flow's size
+at::Tensor flow_finalize(const at::Tensor& flow, int64_t H, int64_t W, int64_t Hp, int64_t Wp) {
+    need_hip(flow, "flow_finalize");
+    TORCH_CHECK(flow.dim() == 4 && flow.size(1) == 2 && H > 0 && W > 0, "dbsr::flow_finalize: flow [P,2,hf,wf], H, W > 0");
+    const int64_t P = flow.size(0), hf = flow.size(2), wf = flow.size(3);
+    if (Hp <= 0) Hp = 4 * hf;
+    if (Wp <= 0) Wp = 4 * wf;
+    auto fl = flow.permute({0, 2, 3, 1}).to(at::kFloat).contiguous();
+    auto out = at::empty({P, 2, H, W}, flow.options().dtype(at::kFloat));
+    check(dbsr_flow_finalize(P, 2, hf, wf, desc(fl, 2), H, W, Hp, Wp, out.data_ptr<float>(), 0.0f, null_desc(),
+                             cur_stream()),
+          "dbsr_flow_finalize");
+    return out.to(flow.scalar_type());
+}
+
+at::Tensor flow_finalize_backward(const at::Tensor& grad, int64_t hf, int64_t wf, int64_t Hp, int64_t Wp) {
+    need_hip(grad, "flow_finalize_backward");
+    TORCH_CHECK(grad.dim() == 4 && grad.size(1) == 2 && hf > 0 && wf > 0, "dbsr::flow_finalize_backward: grad [P,2,H,W]");
+    const int64_t P = grad.size(0), H = grad.size(2), W = grad.size(3);
+    if (Hp <= 0) Hp = 4 * hf;
+    if (Wp <= 0) Wp = 4 * wf;
+    auto g = grad.to(at::kFloat).contiguous();
+    auto out = at::empty({P, hf, wf, 2}, grad.options().dtype(at::kFloat));
+    check(dbsr_flow_finalize_backward(P, hf, wf, H, W, Hp, Wp, g.data_ptr<float>(), desc(out, 2), cur_stream()),
+          "dbsr_flow_finalize_backward");
+    return out.permute({0, 3, 1, 2}).contiguous().to(grad.scalar_type());
+}
+
+// F.interpolate(x, (Hp, Wp), mode='bilinear', align_corners=False), forward only (pwcnet.py:266-271: the images)
+at::Tensor resize_bilinear(const at::Tensor& x, int64_t Hp, int64_t Wp) {
+    need_hip(x, "resize_bilinear");
+    TORCH_CHECK(x.dim() == 4 && Hp > 0 && Wp > 0, "dbsr::resize_bilinear: x [N,C,H,W], Hp, Wp > 0");
+    const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+    auto in = x.to(at::kFloat).contiguous();
+    auto out = at::empty({N, C, Hp, Wp}, x.options().dtype(at::kFloat));
+    check(dbsr_resize_bilinear(N * C, H, W, in.data_ptr<float>(), Hp, Wp, (float)H / (float)Hp, (float)W / (float)Wp,
+                               1.0f, out.data_ptr<float>(), cur_stream()),
+          "dbsr_resize_bilinear");
+    return out.to(x.scalar_type());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dbsr, m) {
+    m.def("conv2d_backward(Tensor grad, Tensor x, Tensor weight, Tensor out, int stride, int padding, int dilation, "
+          "int act, bool need_x, bool need_w, bool need_b) -> (Tensor, Tensor, Tensor)");
+    m.def("conv_transpose2d_k4s2(Tensor x, Tensor weight, Tensor? bias=None) -> Tensor");
+    m.def("conv_transpose2d_k4s2_backward(Tensor grad, Tensor x, Tensor weight, bool need_x, bool need_w, bool need_b) "
+          "-> (Tensor, Tensor, Tensor)");
+    m.def("flow_finalize(Tensor flow, int H, int W, int Hp=0, int Wp=0) -> Tensor");
+    m.def("flow_finalize_backward(Tensor grad, int hf, int wf, int Hp=0, int Wp=0) -> Tensor");
+    m.def("resize_bilinear(Tensor x, int Hp, int Wp) -> Tensor");
     m.def("correlation(Tensor first, Tensor second, bool leaky=False) -> Tensor");
     m.def("correlation_backward(Tensor grad, Tensor first, Tensor second, Tensor out, bool leaky) -> (Tensor, Tensor)");
     m.def("backwarp(Tensor input, Tensor flow) -> Tensor");
@@ -390,4 +630,10 @@ TORCH_LIBRARY_IMPL(dbsr, CUDA, m) {
     m.impl("fuse_softmax", &fuse_softmax);
     m.impl("fuse_backward", &fuse_backward);
     m.impl("conv2d_fused", &conv2d_fused);
+    m.impl("conv2d_backward", &conv2d_backward);
+    m.impl("conv_transpose2d_k4s2", &conv_transpose2d_k4s2);
+    m.impl("conv_transpose2d_k4s2_backward", &conv_transpose2d_k4s2_backward);
+    m.impl("flow_finalize", &flow_finalize);
+    m.impl("flow_finalize_backward", &flow_finalize_backward);
+    m.impl("resize_bilinear", &resize_bilinear);
 }

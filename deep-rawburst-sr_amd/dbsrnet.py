@@ -92,8 +92,8 @@ class DBSRNet(nn.Module):
                          rebuilds the engine.
     In training mode with autograd enabled (net.train(), no torch.no_grad()) the forward keeps its
     activations and `pred` carries a grad_fn: loss.backward() on any objective fills the DBSR parameters'
-    .grad (PWC-Net is frozen, encoders.py:56-61) from the HIP backward kernels, and any torch.optim optimizer
-    steps them (any compute dtype; with float16 scale the loss with torch.amp.GradScaler as usual: this path
+    .grad (and, for a net built with train_alignmentnet=True, PWC-Net's: encoders.py:56-57) from the HIP backward
+    kernels, and any torch.optim optimizer steps them (any compute dtype; with float16 scale the loss with torch.amp.GradScaler as usual: this path
     never scales internally, DBSRTrainer's own step does).  Evaluation (net.eval() or no_grad) runs the
     inference engine.
     """
@@ -139,11 +139,29 @@ class DBSRNet(nn.Module):
             # autograd through the HIP training forward / backward (training.train_forward): the reference's
             # loop -- pred, _ = net(burst); loss.backward(); optimizer.step() -- runs unchanged
             from .training import train_forward
+            if flow is None and getattr(self.encoder, 'train_alignmentnet', False):
+                # encoders.py:52-57: the alignment network is trained too -- its differentiable forward produces
+                # the offsets, and the training forward takes them as an external flow whose gradient it returns
+                flow = alignment_flow(self, im)
             return train_forward(self, im, flow)
         if flow is not None:
             raise NotImplementedError('DBSRNet.forward(flow=...): the inference engine takes no external flows; '
                                       'DBSRTrainer.forward_saved(burst, flow=flow) runs the forward with them')
         return self._get_engine().forward(im)
+
+
+def alignment_flow(net, im):
+    """offsets [B,N-1,2,H,W] of burst im [B,N,4,H,W] from the net's own PWC-Net with autograd to its parameters
+    (encoders.py:52-57 with train_alignmentnet=True)."""
+    x_rgb = torch.stack((im[:, :, 0], im[:, :, 1:3].mean(dim=2), im[:, :, 3]), dim=2)
+    x_ref = x_rgb[:, :1].repeat(1, x_rgb.shape[1] - 1, 1, 1, 1).contiguous()
+    x_oth = x_rgb[:, 1:].contiguous()
+    pwc = net.encoder.alignment_net
+    if not pwc._trains():
+        raise RuntimeError('alignment_flow: the alignment network is not in its differentiable training mode '
+                           '(differentiable=True, train(), grad enabled, a parameter requiring grad)')
+    offsets = pwc(x_oth.view(-1, *x_oth.shape[-3:]), x_ref.view(-1, *x_ref.shape[-3:]))
+    return offsets.view(im.shape[0], im.shape[1] - 1, 2, im.shape[-2], im.shape[-1])
 
 
 def dbsrnet_cvpr2021(enc_init_dim, enc_num_res_blocks, enc_out_dim,
@@ -163,6 +181,7 @@ def dbsrnet_cvpr2021(enc_init_dim, enc_num_res_blocks, enc_out_dim,
     if not use_offset or ref_offset_noise > 0.0:
         raise NotImplementedError('hot path needs use_offset=True and ref_offset_noise=0 (merging.py:91-96)')
     alignment_net = PWCNet(load_pretrained=pwcnet_weights_path is not None, weights_path=pwcnet_weights_path)
+    alignment_net.differentiable = bool(train_alignmentnet)
     encoder = ResEncoderWarpAlignnet(enc_init_dim, enc_num_res_blocks, enc_out_dim, alignment_net,
                                      activation=activation, train_alignmentnet=train_alignmentnet)
     merging = WeightedSum(enc_out_dim, weight_pred_proj_dim, offset_feat_dim,

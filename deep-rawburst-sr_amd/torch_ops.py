@@ -12,11 +12,16 @@ way the reference's _FunctionCorrelation does (external/pwcnet/correlation/corre
     torch.ops.dbsr.backwarp_backward(grad, input, flow)         backwarp's gradients -> (dinput, dflow)
     torch.ops.dbsr.fuse_softmax(logits, feats, want_weights)    merging.py:116-126 -> (fused, weights)
     torch.ops.dbsr.conv2d_fused(x, w, b, stride, padding, dilation, act, residual, post_act)
+    torch.ops.dbsr.conv_transpose2d_k4s2(x, w, b)               nn.ConvTranspose2d(k4, s2, p1), pwcnet.py:119-120
+    torch.ops.dbsr.flow_finalize(flow, H, W)                    pwcnet.py:274-279
+    torch.ops.dbsr.resize_bilinear(x, Hp, Wp)                   pwcnet.py:266-271 (forward only)
 
 Gradients: correlation w.r.t. both inputs (K3/K4), backwarp and warp w.r.t. the sampled tensor and the flow
 (csrc/flow_grad.hip; backwarp's in-place thresholded mask takes none, pwcnet.py:33-38), fusion w.r.t. the
-features / logits.  Only the gradients autograd asks for are computed.  No CPU kernels: like the reference's
-correlation (correlation.py:324-325) the ops raise on CPU tensors.
+features / logits, conv2d_fused (act none / relu / lrelu, no residual or post-activation), conv_transpose2d_k4s2
+and flow_finalize w.r.t. their tensor inputs (csrc/pwc_grad.hip: PWC-Net training).  Only the gradients autograd
+asks for are computed.  No CPU kernels: like the reference's correlation (correlation.py:324-325) the ops raise on
+CPU tensors.
 """
 import os
 
@@ -106,6 +111,57 @@ def _register_autograd():
         return dl, df, None
 
     lib.register_autograd('dbsr::fuse_softmax', fuse_bwd, setup_context=fuse_setup)
+
+    # conv2d_fused: act none / ReLU / LeakyReLU without a residual or post-activation (csrc/pwc_grad.hip and the
+    # stride-1 kernels of train_ops.hip, chosen by dbsr::conv2d_backward)
+    def conv_setup(ctx, inputs, output):
+        x, weight, bias, stride, padding, dilation, act, residual, post_act = inputs
+        if residual is not None or post_act != 0:
+            # the inner activation's output is not kept, so its gradient cannot be formed: fail while recording
+            raise RuntimeError('dbsr::conv2d_fused: autograd needs residual=None and post_act=0')
+        if act not in (_lib.ACT_NONE, _lib.ACT_RELU, _lib.ACT_LRELU):
+            raise RuntimeError('dbsr::conv2d_fused: autograd needs act in {none, relu, lrelu} (got %d)' % act)
+        need_w = ctx.needs_input_grad[1]
+        ctx.save_for_backward(x if need_w else None, weight, output if act != _lib.ACT_NONE else None)
+        ctx.conv = (stride, padding, dilation, act)
+        ctx.x_meta = (x.shape, x.dtype)
+
+    def conv_bwd(ctx, grad):
+        x, weight, out = ctx.saved_tensors
+        stride, padding, dilation, act = ctx.conv
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if x is None:                         # only d/d(input): the kernels read the input's shape and dtype alone
+            x = torch.empty(ctx.x_meta[0], dtype=ctx.x_meta[1], device=grad.device)
+        if out is None:
+            out = grad
+        dx, dw, db = torch.ops.dbsr.conv2d_backward(grad.contiguous(), x, weight, out, stride, padding, dilation, act,
+                                                    need_x, need_w, need_b)
+        return (dx if need_x else None, dw if need_w else None, db if need_b else None,
+                None, None, None, None, None, None)
+
+    lib.register_autograd('dbsr::conv2d_fused', conv_bwd, setup_context=conv_setup)
+
+    def convt_setup(ctx, inputs, output):
+        x, weight, bias = inputs
+        ctx.save_for_backward(x, weight)
+
+    def convt_bwd(ctx, grad):
+        x, weight = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        dx, dw, db = torch.ops.dbsr.conv_transpose2d_k4s2_backward(grad.contiguous(), x, weight, need_x, need_w, need_b)
+        return dx if need_x else None, dw if need_w else None, db if need_b else None
+
+    lib.register_autograd('dbsr::conv_transpose2d_k4s2', convt_bwd, setup_context=convt_setup)
+
+    def ff_setup(ctx, inputs, output):
+        flow, H, W, Hp, Wp = inputs
+        ctx.ff = (flow.shape[2], flow.shape[3], Hp or 4 * flow.shape[2], Wp or 4 * flow.shape[3])
+
+    def ff_bwd(ctx, grad):
+        hf, wf, Hp, Wp = ctx.ff
+        return torch.ops.dbsr.flow_finalize_backward(grad.contiguous(), hf, wf, Hp, Wp), None, None, None, None
+
+    lib.register_autograd('dbsr::flow_finalize', ff_bwd, setup_context=ff_setup)
 
 
 def FunctionCorrelation(tenFirst, tenSecond):

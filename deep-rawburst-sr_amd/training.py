@@ -120,6 +120,13 @@ class DBSRTrainer:
     [B,N-1,2,H,W] (unscaled when a loss scaler runs).  step / forward_backward / forward_saved take `flow`
     ([B,N-1,2,H,W] fp32 on the device): the offsets then come from the caller (an alignment network of their own)
     instead of the package's PWC-Net, in a plan of its own without PWC-Net ops.
+
+    alignment_grad=True (a net built with train_alignmentnet=True; encoders.py:56-57): step(burst, frame_gt) also
+    trains PWC-Net -- its differentiable forward (pwcnet.PWCNet, fp32) gives the flow, the external-flow plan runs
+    with flow_grad, autograd carries flow_grad() into the PWC parameters (csrc/pwc_grad.hip) and dbsr_adam_step
+    runs on a second flat buffer of them with the same lr, betas and eps; pwc_grad_view(p) is a PWC parameter's
+    last gradient.  Not with loss_scale (so not fp16) and not with a world size above 1.  Without it such a net is
+    refused.
     """
     # re-pack every conv's weights in one launch (dbsr_conv_pack_weights_batch, bitwise the per-conv
     # pack / dgrad-transpose / pack launches it replaces: False runs those, for A/B and the equality test)
@@ -130,12 +137,13 @@ class DBSRTrainer:
 
     def __init__(self, net, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, boundary_ignore=40, process_group=None,
                  bucket_bytes=4 << 20, optimizer=True, loss_scale=None, init_scale=65536.0, growth_factor=2.0,
-                 backoff_factor=0.5, growth_interval=2000, flow_grad=False):
+                 backoff_factor=0.5, growth_interval=2000, flow_grad=False, alignment_grad=False):
         dev = next(net.parameters()).device
         if dev.type != 'cuda':
             raise RuntimeError('DBSRTrainer needs the network on a HIP device')
         self.net, self.dev, self.dtype = net, dev, net.compute_dtype
-        self.want_flow_grad = bool(flow_grad)
+        self.alignment_grad = bool(alignment_grad)
+        self.want_flow_grad = bool(flow_grad) or self.alignment_grad
         self._flow_plan = None            # the plan whose dflow buffer holds the last backward's dL/d(offsets)
         # Loss scaling (csrc/loss_scale.hip, torch.amp.GradScaler's rule on the device).  None: no scaling -- the
         # plan and the optimizer launch are the unscaled ones -- except for an fp16 net, where it means 'dynamic':
@@ -167,12 +175,12 @@ class DBSRTrainer:
             self._ls.view(torch.float32)[L.LS_SCALE] = scale0
             self._fb_inf = torch.zeros(1, dtype=torch.int32, device=dev)   # found_inf of the last forward_backward
         self.lr, self.betas, self.eps, self.bi = lr, betas, eps, boundary_ignore
-        if getattr(net.encoder, 'train_alignmentnet', False):
-            # the reference then backpropagates into PWC-Net (encoders.py:56-57); the HIP backward reaches
-            # dL/d(offsets) (flow_grad=True) but PWC-Net itself runs forward-only here, so refuse rather than train
-            # without alignment gradients (an alignment network in torch trains through the `flow` argument)
-            raise NotImplementedError('DBSRTrainer: train_alignmentnet=True (PWC-Net training) is not on the HIP '
-                                      'backward; build the net with train_alignmentnet=False (dbsrnet_cvpr2021 default)')
+        if getattr(net.encoder, 'train_alignmentnet', False) and not self.alignment_grad:
+            # the reference then backpropagates into PWC-Net (encoders.py:56-57); this trainer does so only when
+            # asked (alignment_grad=True), so refuse rather than train without alignment gradients
+            raise NotImplementedError('DBSRTrainer: train_alignmentnet=True (PWC-Net training) needs '
+                                      'alignment_grad=True; or build the net with train_alignmentnet=False '
+                                      '(dbsrnet_cvpr2021 default)')
         softmax, ref_base, self.offset_modulo = merging_variant(net.merging)
         if not (softmax and ref_base):
             # the backward kernels are the softmax's (dbsr_fuse_backward) and the reference-frame base's
@@ -181,6 +189,15 @@ class DBSRTrainer:
                                       'HIP backward (dbsrnet_cvpr2021 defaults: softmax=True, use_base_frame=True)')
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
+        if self.alignment_grad:
+            # later work, both: the PWC backward runs unscaled through autograd, and its gradients are not bucketed
+            if self.scaling:
+                raise NotImplementedError('DBSRTrainer: loss_scale with alignment_grad=True is not supported (the '
+                                          'PWC-Net backward is fp32 and unscaled)')
+            if self.world > 1:
+                raise NotImplementedError('DBSRTrainer: world size > 1 with alignment_grad=True is not supported (the '
+                                          'PWC-Net gradients are not all-reduced)')
+            self._init_alignment(optimizer)
         # PWC-Net runs without gradients (train_alignmentnet=False: encoders.py:58-61); its parameters are left
         # as the caller set them -- they never receive a .grad from this backward
         mods = self._trainable_convs()
@@ -213,6 +230,59 @@ class DBSRTrainer:
 
     def _trainable_convs(self):
         return trainable_convs(self.net)
+
+    def _init_alignment(self, optimizer):
+        """The PWC-Net parameters as a second flat fp32 buffer with its own Adam moments: the reference gives
+        net.parameters() to one Adam (default_synthetic.py:94), so lr, betas, eps and the step count are shared."""
+        pwc = self.net.encoder.alignment_net
+        if not getattr(pwc, 'differentiable', False):
+            raise NotImplementedError('DBSRTrainer: alignment_grad=True needs the package\'s PWCNet with '
+                                      'differentiable=True (dbsrnet_cvpr2021(train_alignmentnet=True))')
+        self.pwc_params = [p for p in pwc.parameters() if p.requires_grad]
+        if not optimizer:
+            return
+        n = sum(p.numel() for p in self.pwc_params)
+        self.pwc_flat = torch.empty(n, dtype=torch.float32, device=self.dev)
+        self.pwc_flat_grad = torch.zeros(n, dtype=torch.float32, device=self.dev)
+        self.pwc_exp_avg = torch.zeros(n, dtype=torch.float32, device=self.dev)
+        self.pwc_exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=self.dev)
+        self.pwc_offset = {}
+        o = 0
+        for p in self.pwc_params:
+            k = p.numel()
+            self.pwc_flat[o:o + k].copy_(p.detach().reshape(-1).float())
+            p.data = self.pwc_flat[o:o + k].view(p.shape)
+            self.pwc_offset[id(p)] = (o, k)
+            o += k
+        self.n_pwc_params = n
+
+    def pwc_grad_view(self, p):
+        """The last step's gradient of PWC-Net parameter p (a view of the flat gradient buffer)."""
+        o, k = self.pwc_offset[id(p)]
+        return self.pwc_flat_grad[o:o + k].view(p.shape)
+
+    def _step_alignment(self, burst, frame_gt):
+        """A step that also trains PWC-Net: its differentiable forward gives the flow, the external-flow plan runs
+        with dL/d(offsets), autograd carries that into the PWC parameters, and both flat buffers take one Adam
+        step."""
+        from .dbsrnet import alignment_flow
+        pwc = self.net.encoder.alignment_net
+        with torch.enable_grad():
+            flow = alignment_flow(self.net, burst.to(torch.float32))
+        loss = self._step_plan(burst, frame_gt, flow.detach())
+        grads = torch.autograd.grad(flow, self.pwc_params, self.flow_grad().to(flow.dtype), allow_unused=True)
+        self.pwc_flat_grad.zero_()
+        for p, g in zip(self.pwc_params, grads):
+            if g is not None:
+                self.pwc_grad_view(p).copy_(g)
+        lib = L.lib()
+        L.check(lib.dbsr_adam_step(self.n_pwc_params, self.pwc_flat.data_ptr(), self.pwc_flat_grad.data_ptr(),
+                                   self.pwc_exp_avg.data_ptr(), self.pwc_exp_avg_sq.data_ptr(), self.lr, self.betas[0],
+                                   self.betas[1], self.eps, self.step_count, 1.0, L.stream_ptr(self.dev)), 'adam (PWC)')
+        # the parameters changed through their storage: packed copies keyed by tensor version are stale
+        torch.ops.dbsr.clear_pack_cache()
+        pwc._engine = None
+        return loss
 
     def grad_view(self, p):
         o, k = self.offset[id(p)]
@@ -564,7 +634,13 @@ class DBSRTrainer:
     # ------------------------------------------------------------------------------------------------
     def step(self, burst, frame_gt, flow=None):
         """One training step on this rank's bursts [B,N,4,H,W] and ground truth [B,3,sH,sW] (flow: the caller's
-        offsets [B,N-1,2,H,W] instead of PWC-Net's); returns the rank-local loss (device tensor, shape [1])."""
+        offsets [B,N-1,2,H,W] instead of PWC-Net's); returns the rank-local loss (device tensor, shape [1]).  With
+        alignment_grad=True and no `flow`, PWC-Net is trained too."""
+        if self.alignment_grad and flow is None:
+            return self._step_alignment(burst, frame_gt)
+        return self._step_plan(burst, frame_gt, flow)
+
+    def _step_plan(self, burst, frame_gt, flow=None):
         plan = self._load(burst, frame_gt, flow)
         stream = L.stream_ptr(self.dev)
         # segments of the op list between the gradient buckets' completion points: each segment is one HIP
@@ -767,6 +843,9 @@ class DBSRRealWorldTrainer(DBSRTrainer):
             # op) and is not scaled yet: refuse before anything is allocated
             raise ValueError('DBSRRealWorldTrainer: train in torch.bfloat16 or torch.float32 (the aligned objective '
                              'has no loss scaling here)')
+        if kwargs.get('alignment_grad'):
+            raise NotImplementedError('DBSRRealWorldTrainer: alignment_grad=True is not supported (the real-world '
+                                      'step has its own segments; train PWC-Net with DBSRTrainer)')
         super().__init__(net, boundary_ignore=boundary_ignore, **kwargs)
         from .burstsr import SpatialColorAlignment
         if self.s != 2 * sr_factor:
@@ -947,7 +1026,8 @@ def train_forward(net, burst, flow=None):
     caller supplies the offsets (flow [B,N-1,2,H,W], e.g. their own alignment network's output), to that flow."""
     eng = getattr(net, '_train_engine', None)
     if eng is None or eng.net is not net or eng.dtype != net.compute_dtype or not _aliased(eng):
-        eng = net._train_engine = DBSRTrainer(net, optimizer=False)
+        eng = net._train_engine = DBSRTrainer(net, optimizer=False,
+                                              alignment_grad=bool(getattr(net.encoder, 'train_alignmentnet', False)))
     pred, offs, fw = _DBSRTrainForward.apply(burst, eng, flow, *eng.params)
     from .engine import DBSRAux
     return pred, DBSRAux(offs, fw)

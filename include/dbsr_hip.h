@@ -657,6 +657,50 @@ int dbsr_loss_scale_update(void* state, float growth_factor, float backoff_facto
  * dbsr_conv_pack_weights(cout = cin, cin = cout). */
 int dbsr_dgrad_weights(const float* w, int cout, int cin, int kh, int kw, float* wt, void* stream);
 
+/* ---------------- PWC-Net training (csrc/pwc_grad.hip; exports added under ABI 23) ----------------
+ * Gradients of the alignment network's convolutions (models/alignment/pwcnet.py:41-231) that the stride-1 3x3
+ * kernels above do not cover, for the conv family k in {1, 3, 4} (square), stride 1 | 2, dilation >= 1, pad >= 0,
+ * out_h = (in_h + 2 pad - dilation (k - 1) - 1) / stride + 1 (both sizes are passed: a stride-2 conv maps 5 and 6
+ * input rows to the same 3 output rows).  NHWC slices of one dtype (f32 / bf16 / f16), ld and c0 multiples of 16
+ * bytes, the slice rounded up to 16 bytes inside the pixel; fp32 accumulation on MFMA (16-bit: 16x16x32; f32: the
+ * true-fp32 16x16x4); no float atomics, two runs are bitwise equal; no host synchronisation.  Anything else is
+ * refused with DBSR_E_ARG before any launch.
+ *
+ * dbsr_conv_wgrad_sd: dw[co][ci][ky][kx] (fp32, torch layout) (+)= sum over n, oy, ox of dy[n, oy, ox, co] *
+ *   x[n, oy stride - pad + ky dilation, ox stride - pad + kx dilation, ci] (0 outside the image); db[co] (+)= sum
+ *   of dy (db NULL: none).  Every element of dw (and db) is written.  Pad channels of x / dy are never summed into
+ *   a real output.  workspace: >= dbsr_conv_wgrad_sd_workspace_bytes, 16-byte aligned; per-block fp32 partials
+ *   added in block order.
+ *   ConvTranspose2d(k4, s2, p1): its weight gradient is this call with the roles swapped -- x = the transposed
+ *   conv's dy [n][2h][2w] (its cout channels as `cin`), dy = its input [n][h][w] (its cin channels as `cout`),
+ *   k 4, stride 2, pad 1: dw is torch's [cin][cout][4][4].  (Its input gradient is dbsr_conv2d with kh = kw = 4,
+ *   stride 2, pad 1 over dy, weights [cin][cout][4][4] packed as they are; its bias gradient dbsr_chan_sum.)
+ * dbsr_conv_dgrad_sd: dx[n, iy, ix, ci] = sum over ky, kx, co of dy[n, (iy + pad - ky dilation) / stride,
+ *   (ix + pad - kx dilation) / stride, co] * w[co][ci][ky][kx] over the taps whose divisions are exact and in
+ *   range: a gather with one GEMM per (iy mod stride, ix mod stride) class over that class's live taps only (for
+ *   k3 s2 p1: 1, 2, 2 and 4 of the 9).  Every pixel's channels [c0, c0 + cin rounded up to 16 bytes) are written,
+ *   the pad as zeros.  dy's channels between cout and the next 16 bytes must be finite (they meet zero weights).
+ *   w_packed: dbsr_dgrad_sd_pack of the conv's weights in dx's dtype ([tap][round_up(cin, 16)][round_up(cout, 32)]).
+ *   For stride 1 the result equals dbsr_conv2d with dbsr_dgrad_weights up to summation order. */
+size_t dbsr_conv_wgrad_sd_workspace_bytes(int n, int out_h, int out_w, int cin, int cout, int k);
+int dbsr_conv_wgrad_sd(int n, int in_h, int in_w, dbsr_tensor x, int cin, int out_h, int out_w, dbsr_tensor dy,
+                       int cout, int k, int stride, int dil, int pad, float* dw, float* db, int accumulate,
+                       void* workspace, size_t workspace_bytes, void* stream);
+size_t dbsr_dgrad_sd_packed_elems(int cout, int cin, int k);
+int dbsr_dgrad_sd_pack(const float* w, int cout, int cin, int k, int dtype, void* w_packed, void* stream);
+int dbsr_conv_dgrad_sd(int n, int in_h, int in_w, dbsr_tensor dx, int cin, int out_h, int out_w, dbsr_tensor dy,
+                       int cout, int k, int stride, int dil, int pad, const void* w_packed, void* stream);
+/* dpre = dy * act'(y) for act = DBSR_ACT_RELU / DBSR_ACT_LRELU (y = the activation's output; slope 0.1 where
+ * y <= 0): dy itself, 0, or 0.1f * dy rounded once to the dtype.  n images of hw pixels, c channels; a thread owns
+ * 8 channels, so the slices rounded up to 8 channels must stay inside the pixel; dpre's pad channels are zeros. */
+int dbsr_act_backward(int n, int hw, int c, int act, dbsr_tensor dy, dbsr_tensor y, dbsr_tensor dpre, void* stream);
+/* The transpose of dbsr_flow_finalize's offsets output: dflow (fp32 NHWC 2-channel slice [P][hf][wf]) =
+ * sum over the fine pixels of their bilinear weight on this coarse pixel (align_corners=False, PyTorch's source
+ * index with its clamp at 0) * 20 * (W / Wp, H / Hp) * doffsets [P][2][H][W] (fp32).  A gather per coarse pixel
+ * (up- and down-sampling), summed in double and rounded once: deterministic. */
+int dbsr_flow_finalize_backward(int P, int hf, int wf, int H, int W, int Hp, int Wp, const float* doffsets,
+                                dbsr_tensor dflow, void* stream);
+
 /* n NHWC images (c channels from in.c0, any dtype) -> fp32 NCHW out [n][c][hw]: the fusion weights in the
  * reference's [B,N,C,H,W] fp32 layout (merging.py:117-126), materialised when a caller reads them. */
 int dbsr_nhwc_to_nchw_f32(int n, int hw, int c, dbsr_tensor in, float* out, void* stream);
