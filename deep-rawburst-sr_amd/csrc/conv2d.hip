@@ -1704,7 +1704,7 @@ int launch_ws(const ConvK& k, const dbsr_conv_desc* d, int px, hipStream_t s) {
 }
 
 int g_ks128_enabled = 1;
-// the K-split weight-stationary 128-channel kernel (conv128.hip) serves `d`: 16-bit 3x3/s1/p1/d1, 96 < cin <= 128,
+// the cout-split weight-stationary 128-channel kernel (conv128.hip) serves `d`: 16-bit 3x3/s1/p1/d1, 96 < cin <= 128,
 // cout == 128, aligned NHWC output / residual / gate, frames a multiple of 16 x 8, the whole image (no plan_h slab)
 // and at least 128 tiles (the weight predictor's input conv and ResBlocks, merging.py:86-90, 98-101, and their
 // gated dgrads in the training step)

@@ -149,15 +149,16 @@ int dbsr_weights_round_diffuse(const float* w, int cout, int cin, int kh, int kw
  * applies (3x3, stride 1, pad == dilation in {1,2,4,8}, cin > 16, out >= 8x8, NHWC out), else the
  * generic implicit-GEMM kernel; 1 = no pipelined kernel; 0 = generic kernel only; 3 = as 2 but the
  * pipelined kernel at any tile count (tests); 4 = as 2 without the weight-stationary kernels (both the Cin <= 64
- * one and the K-split 128-channel one); 5 = as 2 without the K-split 128-channel kernel (ABI 21).  Under 2 the
+ * one and the 128-channel one); 5 = as 2 without the 128-channel weight-stationary kernel (ABI 21).  Under 2 the
  * 16-bit 128 -> 128 3x3/s1/p1 convs of >= 128 tiles of 16 x 8 pixels (merging.py:86-90, 98-101: the weight
- * predictor's input conv and ResBlocks) run on the K-split weight-stationary kernel (kernel_for 7), which sums
- * each output as (input channels 0-63) + (64-127) in fp32, not in the pipelined kernel's order. */
+ * predictor's input conv and ResBlocks) run on the 128-channel weight-stationary kernel (kernel_for 7: each wave
+ * holds 16 couts over the whole K and rolls the tile's halo rows through them), which sums each output as one
+ * in-order fp32 chain over (32-channel chunk, tap) from zero, then the bias. */
 int dbsr_set_conv_algo(int algo);
 /* Which kernel dbsr_conv2d would launch for `d` under the current selection: 5 pointwise projection
  * (16-bit 1x1, cin 32..512 a power of two, cout 32 | 64, no residual: merging.py:34), 4 weight-stationary,
  * 3 PixelShuffle upsampler (bf16 1x1 with DBSR_OUT_SHUFFLE, 32 channels per sub-pixel), 2 pipelined,
- * 6 narrow-output 3x3 (16-bit, cout <= 4, cin >= 256, pad 1: the PWC level-2 flow head), 7 K-split
+ * 6 narrow-output 3x3 (16-bit, cout <= 4, cin >= 256, pad 1: the PWC level-2 flow head), 7 cout-split
  * weight-stationary 128 -> 128 3x3 (ABI 21), 8 small-input 3x3 (16-bit, cin <= 8, cout a multiple of 16 up to 64,
  * no residual / gate: the encoder's and offset-feature extractor's first convs, ABI 21), 1 LDS-tiled, 0 generic. */
 int dbsr_conv_kernel_for(const dbsr_conv_desc* d);

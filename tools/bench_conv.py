@@ -1,5 +1,7 @@
 """Microbenchmark of dbsr_conv2d on the cfg2 hot shapes: kernel selections (dbsr_set_conv_algo) side by side, fp16.
-Usage: python tools/bench_conv.py"""
+Each time is followed by the kernel family and dispatch variant that ran; DBSR_HIP_LIB selects another build of the
+library for A/B runs.
+Usage: python tools/bench_conv.py [--only wp.] [--algos 2]"""
 import os
 import sys
 import torch
@@ -51,16 +53,20 @@ def main():
         plan = Plan()
         if 'res' in name or 'post' in name or 'pre' in name:
             r = NHWC(F, H, W, max(8, (cout + 7) // 8 * 8), dt, dev)
-            plan.conv(name, pc, F, x, 0, (H, W), y, 0, L.ACT_NONE, res=r, post_act=L.ACT_RELU)
+            d = plan.conv(name, pc, F, x, 0, (H, W), y, 0, L.ACT_NONE, res=r, post_act=L.ACT_RELU)
         else:
-            plan.conv(name, pc, F, x, 0, (H, W), y, 0, L.ACT_RELU)
+            d = plan.conv(name, pc, F, x, 0, (H, W), y, 0, L.ACT_RELU)
         flop = plan.work[0][1]
         plan.finalize_workspace(dev)
         out = []
         for algo in algos:
             L.lib().dbsr_set_conv_algo(algo)
             ms = plan.time_ops(s, reps=args.reps)[0][1]
-            out.append('%s %7.1f us %6.1f TF/s' % (['generic', 'tiled', 'auto', 'pipe', 'no-ws', 'ws8'][algo], ms * 1e3, flop / ms / 1e9))
+            # kernel family and dispatch variant of this selection (7 / 7001608: conv3x3_ks128, tile 16 x 8), so that an
+            # A/B log shows which kernel each time belongs to
+            kv = 'k%d v%d' % (L.lib().dbsr_conv_kernel_for(d), L.lib().dbsr_conv_dispatch_variant(d))
+            out.append('%s %7.1f us %6.1f TF/s [%s]' % (['generic', 'tiled', 'auto', 'pipe', 'no-ws', 'ws8'][algo], ms * 1e3,
+                                                       flop / ms / 1e9, kv))
         L.lib().dbsr_set_conv_algo(2)
         print(f'{name:22s} ' + ' | '.join(out))
 
