@@ -217,6 +217,13 @@ def lib():
                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
             'dbsr_ssim_backward': ([c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+            'dbsr_lpips_prep': ([c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p], c_int),
+            'dbsr_maxpool2d': ([c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                c_void_p], c_int),
+            'dbsr_lpips_layer_workspace_bytes': ([c_int, c_int, c_int, c_int], c_size_t),
+            'dbsr_lpips_layer': ([c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_size_t, c_void_p], c_int),
             'dbsr_unprocess_rgb': ([c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
             'dbsr_burst_synth': ([c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p], c_int),
@@ -256,6 +263,7 @@ EXPORTED = ['dbsr_abi_version', 'dbsr_last_error', 'dbsr_conv_packed_elems', 'db
             'dbsr_pwc_extract_supported', 'dbsr_pwc_level_prep', 'dbsr_pwc_level_prep_supported',
             'dbsr_aligned_l1_workspace_bytes', 'dbsr_aligned_l1_forward', 'dbsr_aligned_l1_backward',
             'dbsr_ssim_workspace_bytes', 'dbsr_ssim_forward', 'dbsr_ssim_backward',
+            'dbsr_lpips_prep', 'dbsr_maxpool2d', 'dbsr_lpips_layer_workspace_bytes', 'dbsr_lpips_layer',
             'dbsr_unprocess_rgb', 'dbsr_burst_synth', 'dbsr_postprocess_rgb']
 
 

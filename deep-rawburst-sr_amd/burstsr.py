@@ -14,7 +14,8 @@ least-squares fit, models/loss/spatial_color_alignment.py:23-108) and reporting 
   * `BurstSRDataset` + `IndexedBurst` ordering (burstsr_dataset.py:243-291; sampler.py:99-150).
   * `SpatialColorAlignment` / `match_colors` on the HIP path: PWC flow from the engine, warps from the
     warp kernel, resampling / smoothing / colour fit / mask from csrc/sca_ops.hip.
-  * `compute_score_burstsr` (compute_score.py:96-134, PSNR and SSIM columns; LPIPS is out of scope).
+  * `compute_score_burstsr` (compute_score.py:96-134, PSNR and SSIM columns; LPIPS when given an
+    evaluation.LPIPS module built with the caller's weights).
   * Training use (actors/dbsr_actors.py:68-80): `SpatialColorAlignment.forward` carries autograd to the
     prediction, `PixelWiseError('l1', boundary_ignore)` with `valid=` is the objective, `PSNR(..., valid=)`
     the statistic; the fused step is training.DBSRRealWorldTrainer (csrc/sca_train.hip).
@@ -501,15 +502,19 @@ def write_burstsr_sample(root, name, frames_raw, gt_raw, meta_samsung, meta_cano
 
 # ------------------------------------------------------------------------------------- harness
 
-def compute_score_burstsr(net, dataset, alignment_net, boundary_ignore=40, burst_sz=None, device='cuda'):
+def compute_score_burstsr(net, dataset, alignment_net, boundary_ignore=40, burst_sz=None, device='cuda', lpips=None):
     """compute_score.py:96-134 (PSNR and SSIM columns): per burst net(burst) -> quantise to 2^14 -> spatial +
     colour alignment to the ground truth -> PSNR and SSIM over the valid mask with boundary_ignore; mean over the
     set.  Returns {'psnr': mean, 'per_image': {burst_name: psnr}, 'ssim': mean, 'per_image_ssim': {burst_name:
-    ssim}} (LPIPS, the reference's third metric, is not computed)."""
+    ssim}}.  `lpips`, an evaluation.LPIPS module built with the caller's weights and this boundary_ignore (on
+    `device`), adds the reference's third column as 'lpips' (the mean) and 'per_image_lpips': LPIPS of the aligned
+    prediction, with the mask ignored as in the reference (image_quality_v2.py:152)."""
+    from .evaluation import _lpips_column
+    lpips_fn = _lpips_column(lpips, boundary_ignore, 'compute_score_burstsr')
     sca = SpatialColorAlignment(alignment_net, sr_factor=4)
     psnr_fn = PSNR(boundary_ignore=boundary_ignore)
     ssim_fn = SSIM(boundary_ignore=boundary_ignore, use_for_loss=False)
-    per, per_ssim = {}, {}
+    per, per_ssim, per_lp = {}, {}, {}
     for idx in range(len(dataset)):
         burst, gt, info = dataset[idx]
         burst = burst.unsqueeze(0).to(device)
@@ -522,5 +527,11 @@ def compute_score_burstsr(net, dataset, alignment_net, boundary_ignore=40, burst
             pred_m, valid = sca(pred, gt, burst)
         per[info['burst_name']] = float(psnr_fn(pred_m, gt, valid=valid))
         per_ssim[info['burst_name']] = float(ssim_fn(pred_m, gt, valid=valid))
-    return {'psnr': sum(per.values()) / max(1, len(per)), 'per_image': per,
-            'ssim': sum(per_ssim.values()) / max(1, len(per_ssim)), 'per_image_ssim': per_ssim}
+        if lpips_fn is not None:
+            with torch.no_grad():
+                per_lp[info['burst_name']] = float(lpips_fn(pred_m, gt, valid=valid))
+    res = {'psnr': sum(per.values()) / max(1, len(per)), 'per_image': per,
+           'ssim': sum(per_ssim.values()) / max(1, len(per_ssim)), 'per_image_ssim': per_ssim}
+    if lpips_fn is not None:
+        res.update(lpips=sum(per_lp.values()) / max(1, len(per_lp)), per_image_lpips=per_lp)
+    return res

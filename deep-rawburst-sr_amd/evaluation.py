@@ -15,13 +15,16 @@ can score the drop-in network on the same files:
   * `quantize_prediction` (compute_score.py:109-111) and `PSNR` / `PixelWiseError`
     (models/loss/image_quality_v2.py:24-101), `SSIM` (image_quality_v2.py:104-136 over
     models/loss/msssim.py:10-74), `MSSSIM` (msssim.py:77-103), `compute_score` (compute_score.py:36-122,
-    PSNR and SSIM columns, MS-SSIM on request) and `save_results` (save_results.py:36-67).  The last
-    column, LPIPS, is absent: it needs the `lpips` package's AlexNet / VGG weights and linear heads.
+    PSNR and SSIM columns, MS-SSIM on request) and `save_results` (save_results.py:36-67).
+  * `LPIPS` (image_quality_v2.py:139-163 over the `lpips` package's v0.1 metric, restated), the last column:
+    reported when the caller hands over the package's AlexNet / VGG weights and linear heads
+    (`compute_score(..., lpips=LPIPS(weights=...))`).  No weights are shipped or downloaded.
 
 Host-side Python only: the network forward is the HIP path; PSNR runs as torch ops on whatever device
 the predictions live on; SSIM on device tensors runs the HIP kernels of csrc/metrics.hip (forward and
 gradient), on CPU tensors a torch restatement of the reference arithmetic.  MS-SSIM is host-side only: a
-torch restatement on CPU tensors.
+torch restatement on CPU tensors.  LPIPS on device tensors runs the HIP plan of ops.LPIPSPlan (csrc/lpips.hip
+and the fp32 convs; forward only), on CPU tensors a torch restatement.
 """
 import math
 import os
@@ -462,7 +465,312 @@ class MSSSIM(nn.Module):
         return 1.0 - value if self.use_for_loss else value
 
 
+# ------------------------------------------------------------------------------------------ LPIPS
+#
+# image_quality_v2.LPIPS (:139-163) calls lpips.LPIPS(net)(pred, gt) with the package's normalize=False on [0, 1]
+# images.  The package is neither in the reference tree nor installed; what follows restates its published v0.1
+# code ('LPIPS').  Weights come from the caller: none are shipped and none are downloaded.
+
+LPIPS_SHIFT = (-.030, -.088, -.188)
+LPIPS_SCALE = (.458, .448, .450)
+LPIPS_EPS = 1e-10
+# per net: the convs (cin, cout, k, stride, pad), the torchvision `features` index of each, the package's slice
+# (1..5) each sits in, the program (conv index | 'tap' | ('pool', k, s)) and the smallest crop side
+LPIPS_NETS = {
+    'alex': dict(
+        convs=[(3, 64, 11, 4, 2), (64, 192, 5, 1, 2), (192, 384, 3, 1, 1), (384, 256, 3, 1, 1), (256, 256, 3, 1, 1)],
+        features=[0, 3, 6, 8, 10], slices=[1, 2, 3, 4, 5],
+        program=[0, 'tap', ('pool', 3, 2), 1, 'tap', ('pool', 3, 2), 2, 'tap', 3, 'tap', 4, 'tap'],
+        min_side=31),       # conv1 gives (n - 7) // 4 + 1, the pools (m - 3) // 2 + 1: the second pool needs n >= 31
+    'vgg': dict(
+        convs=[(3, 64, 3, 1, 1), (64, 64, 3, 1, 1), (64, 128, 3, 1, 1), (128, 128, 3, 1, 1), (128, 256, 3, 1, 1),
+               (256, 256, 3, 1, 1), (256, 256, 3, 1, 1), (256, 512, 3, 1, 1), (512, 512, 3, 1, 1),
+               (512, 512, 3, 1, 1), (512, 512, 3, 1, 1), (512, 512, 3, 1, 1), (512, 512, 3, 1, 1)],
+        features=[0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28], slices=[1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5],
+        program=[0, 1, 'tap', ('pool', 2, 2), 2, 3, 'tap', ('pool', 2, 2), 4, 5, 6, 'tap', ('pool', 2, 2), 7, 8, 9,
+                 'tap', ('pool', 2, 2), 10, 11, 12, 'tap'],
+        min_side=16),       # four 2 x 2 pools, each m // 2: the fourth needs n >= 16
+}
+
+
+def lpips_tap_channels(net):
+    """The channel counts of the five tapped layers."""
+    spec, out, last = LPIPS_NETS[net], [], None
+    for op in spec['program']:
+        if isinstance(op, int):
+            last = spec['convs'][op][1]
+        elif op == 'tap':
+            out.append(last)
+    return out
+
+
+def lpips_state_dict_shapes(net):
+    """Key -> shape of the package's LPIPS.state_dict() layout, in the order `generate_lpips_state_dict` documents:
+    the backbone convs in network order (weight, then bias), then the five heads."""
+    spec = _lpips_spec(net)
+    shapes = {}
+    for (cin, cout, k, _, _), fi, sl in zip(spec['convs'], spec['features'], spec['slices']):
+        shapes['net.slice%d.%d.weight' % (sl, fi)] = (cout, cin, k, k)
+        shapes['net.slice%d.%d.bias' % (sl, fi)] = (cout,)
+    for l, c in enumerate(lpips_tap_channels(net)):
+        shapes['lin%d.model.1.weight' % l] = (1, c, 1, 1)
+    return shapes
+
+
+def generate_lpips_state_dict(net='alex', seed=0):
+    """Seeded stand-in weights in the package's state_dict layout, for tests and benchmarks (NOT the trained
+    metric).  Like weights.generate_state_dict, each tensor is drawn from its own numpy PCG64 stream seeded with
+    [seed, crc32(key)], so the values do not depend on the order of generation; the keys are those of
+    `lpips_state_dict_shapes`.  Conv weights are uniform in +-sqrt(6 / fan_in) (activations keep their scale
+    through thirteen ReLU layers), biases uniform in +-0.1, heads uniform in [0, 2 / C): non-negative, like the
+    trained ones.  Returns float32 torch tensors."""
+    out = {}
+    for key, shp in lpips_state_dict_shapes(net).items():
+        rng = np.random.Generator(np.random.PCG64([int(seed), zlib.crc32(key.encode())]))
+        if key.startswith('lin'):
+            arr = rng.uniform(0.0, 2.0 / shp[1], size=shp)
+        elif key.endswith('.bias'):
+            arr = rng.uniform(-0.1, 0.1, size=shp)
+        else:
+            bound = math.sqrt(6.0 / (shp[1] * shp[2] * shp[3]))
+            arr = rng.uniform(-bound, bound, size=shp)
+        out[key] = torch.from_numpy(arr.astype(np.float32))
+    return out
+
+
+def _lpips_spec(net):
+    if net not in LPIPS_NETS:
+        raise ValueError("lpips: type must be 'alex' or 'vgg', not %r" % (net,))
+    return LPIPS_NETS[net]
+
+
+def _lpips_file(src):
+    return torch.load(src, map_location='cpu', weights_only=True) if isinstance(src, (str, os.PathLike)) else src
+
+
+def load_lpips_weights(weights, net='alex', heads=None):
+    """Caller-supplied LPIPS weights -> {'net', 'conv_w': [...], 'conv_b': [...], 'lin': [5 x [C]]} of float32 CPU
+    tensors.  `weights` (and `heads`) may be a file path (read with torch.load(weights_only=True)) or the object:
+
+      (a) the package's LPIPS.state_dict(): net.slice{1..5}.{i}.weight|bias with i the torchvision `features`
+          index, lin{0..4}.model.1.weight [1, C, 1, 1] (duplicates under lins.{l}.model.1.weight are accepted),
+          optional scaling_layer.shift|scale (which must hold the v0.1 constants the kernels use);
+      (b) a torchvision backbone state_dict (features.{i}.weight|bias; classifier.* is ignored) with the package's
+          head file as `heads` (lin{l}.model.1.weight);
+      (c) a tuple (conv_weights, conv_biases, lins) of lists of tensors in network order.
+
+    Every shape is validated; every missing or unexpected key is named in the ValueError."""
+    spec = _lpips_spec(net)
+    chans = lpips_tap_channels(net)
+    weights, heads = _lpips_file(weights), _lpips_file(heads)
+    problems = []
+    if isinstance(weights, (tuple, list)):
+        if len(weights) != 3 or heads is not None:
+            raise ValueError('lpips weights: the list layout is (conv_weights, conv_biases, lins), without `heads`')
+        cw, cb, lins = (list(v) for v in weights)
+        if (len(cw), len(cb), len(lins)) != (len(spec['convs']), len(spec['convs']), 5):
+            raise ValueError('lpips weights (%s): expected %d conv weights, %d conv biases and 5 heads, got %d, %d, %d'
+                             % (net, len(spec['convs']), len(spec['convs']), len(cw), len(cb), len(lins)))
+        names = (['conv_weights[%d]' % i for i in range(len(cw))], ['conv_biases[%d]' % i for i in range(len(cb))],
+                 ['lins[%d]' % i for i in range(5)])
+    elif isinstance(weights, dict):
+        sd = dict(weights)
+        if heads is not None:
+            if not isinstance(heads, dict):
+                raise ValueError('lpips weights: `heads` must be a state_dict (lin{l}.model.1.weight)')
+            sd.update(heads)
+        torchvision = any(k.startswith('features.') for k in sd)
+        wk = [('features.%d' % fi) if torchvision else ('net.slice%d.%d' % (sl, fi))
+              for fi, sl in zip(spec['features'], spec['slices'])]
+        names = ([k + '.weight' for k in wk], [k + '.bias' for k in wk], [])
+        for l in range(5):
+            k = 'lin%d.model.1.weight' % l
+            names[2].append(k if k in sd or ('lins.%d.model.1.weight' % l) not in sd else 'lins.%d.model.1.weight' % l)
+        known = set(names[0]) | set(names[1]) | set(names[2])
+        known |= {'lin%d.model.1.weight' % l for l in range(5)} | {'lins.%d.model.1.weight' % l for l in range(5)}
+        known |= {'scaling_layer.shift', 'scaling_layer.scale'}
+        extra = sorted(k for k in sd if k not in known and not (torchvision and k.startswith('classifier.')))
+        missing = [k for group in names for k in group if k not in sd]
+        if missing:
+            problems.append('missing keys %s' % missing)
+        if extra:
+            problems.append('unexpected keys %s' % extra)
+        for key, ref in (('scaling_layer.shift', LPIPS_SHIFT), ('scaling_layer.scale', LPIPS_SCALE)):
+            if key in sd:
+                t = torch.as_tensor(sd[key]).detach().float().reshape(-1)
+                if t.numel() != 3 or not torch.equal(t, torch.tensor(ref, dtype=torch.float32)):
+                    problems.append('%s %s is not the v0.1 constant %s' % (key, t.tolist(), list(ref)))
+        if problems:
+            raise ValueError('lpips weights (%s): %s' % (net, '; '.join(problems)))
+        cw, cb, lins = ([sd[k] for k in group] for group in names)
+    else:
+        raise ValueError('lpips weights: expected a state_dict, a (conv_weights, conv_biases, lins) tuple or a file '
+                         'path, not %s' % type(weights).__name__)
+    out = {'net': net, 'conv_w': [], 'conv_b': [], 'lin': []}
+    for i, (cin, cout, k, _, _) in enumerate(spec['convs']):
+        w, b = torch.as_tensor(cw[i]).detach(), torch.as_tensor(cb[i]).detach()
+        if tuple(w.shape) != (cout, cin, k, k):
+            problems.append('%s has shape %s, expected %s' % (names[0][i], tuple(w.shape), (cout, cin, k, k)))
+        if tuple(b.shape) != (cout,):
+            problems.append('%s has shape %s, expected %s' % (names[1][i], tuple(b.shape), (cout,)))
+        out['conv_w'].append(w.float().cpu().contiguous())
+        out['conv_b'].append(b.float().cpu().contiguous())
+    for l, c in enumerate(chans):
+        v = torch.as_tensor(lins[l]).detach()
+        if tuple(v.shape) not in ((1, c, 1, 1), (c,)):
+            problems.append('%s has shape %s, expected %s' % (names[2][l], tuple(v.shape), (1, c, 1, 1)))
+        out['lin'].append(v.float().cpu().reshape(-1).contiguous())
+    if problems:
+        raise ValueError('lpips weights (%s): %s' % (net, '; '.join(problems)))
+    return out
+
+
+def lpips_prepare(pred, gt, boundary_ignore=None, bgr2rgb=False):
+    """image_quality_v2.LPIPS.forward :153-159: the channel flip, then the boundary crop."""
+    if bgr2rgb:
+        pred, gt = pred[..., [2, 1, 0], :, :].contiguous(), gt[..., [2, 1, 0], :, :].contiguous()
+    bi = boundary_ignore or 0
+    if bi:
+        pred, gt = pred[..., bi:-bi, bi:-bi], gt[..., bi:-bi, bi:-bi]
+    return pred, gt
+
+
+def _lpips_check_crop(net, h, w):
+    need = _lpips_spec(net)['min_side']
+    if h < need or w < need:
+        raise ValueError('lpips (%s): the crop %d x %d is smaller than %d x %d (the last pool needs a row)'
+                         % (net, h, w, need, need))
+
+
+def lpips_features(x, weights, normalize=False):
+    """The five tapped ReLU outputs of the backbone for [N, 3, H, W] images (already flipped and cropped), after
+    the optional 2x - 1 and the scaling layer (x - shift) / scale.  Torch ops in x's dtype; the float32 constants
+    are cast up as type promotion does in the package."""
+    spec = _lpips_spec(weights['net'])
+    _lpips_check_crop(weights['net'], x.shape[-2], x.shape[-1])
+    if normalize:
+        x = 2 * x - 1
+    shift = torch.tensor(LPIPS_SHIFT, dtype=torch.float32).to(device=x.device, dtype=x.dtype).view(1, 3, 1, 1)
+    scale = torch.tensor(LPIPS_SCALE, dtype=torch.float32).to(device=x.device, dtype=x.dtype).view(1, 3, 1, 1)
+    x = (x - shift) / scale
+    taps = []
+    for op in spec['program']:
+        if isinstance(op, int):
+            _, _, _, s, p = spec['convs'][op]
+            x = F.relu(F.conv2d(x, weights['conv_w'][op].to(x), weights['conv_b'][op].to(x), stride=s, padding=p))
+        elif op == 'tap':
+            taps.append(x)
+        else:
+            x = F.max_pool2d(x, op[1], op[2])
+    return taps
+
+
+def lpips_layer_map(f0, f1, lin):
+    """d[b, y, x] = sum_c lin[c] (n(f0) - n(f1))^2 with n(f) = f / (sqrt(sum_c f^2) + 1e-10), for [B, C, h, w]."""
+    n0 = f0 / (f0.pow(2).sum(dim=1, keepdim=True).sqrt() + LPIPS_EPS)
+    n1 = f1 / (f1.pow(2).sum(dim=1, keepdim=True).sqrt() + LPIPS_EPS)
+    return ((n0 - n1).pow(2) * lin.to(f0).view(1, -1, 1, 1)).sum(dim=1)
+
+
+def lpips_maps(pred, gt, weights, normalize=False):
+    """The five per-layer distance maps [B, h_l, w_l] of already flipped and cropped [B, 3, H, W] images; both
+    images go through the backbone as one batch."""
+    B = pred.shape[0]
+    taps = lpips_features(torch.cat([pred, gt], 0), weights, normalize)
+    return [lpips_layer_map(f[:B], f[B:], lin) for f, lin in zip(taps, weights['lin'])]
+
+
+def lpips_value(pred, gt, weights, normalize=False):
+    """(value [B], per_layer [B, 5], maps): per_layer is each map's mean over y, x; value their sum in layer order."""
+    maps = lpips_maps(pred, gt, weights, normalize)
+    per_layer = torch.stack([m.mean(dim=(1, 2)) for m in maps], 1)
+    value = per_layer[:, 0]
+    for l in range(1, 5):
+        value = value + per_layer[:, l]
+    return value, per_layer, maps
+
+
+class LPIPS(nn.Module):
+    """models/loss/image_quality_v2.py:139-163 over lpips.LPIPS(net=type) (v0.1, spatial=False), restated: the
+    optional channel flip [2,1,0], the boundary crop, the metric, the mean over the batch (`per_image`: [B]
+    instead).  Images go in as they are, [0, 1], with the package's normalize=False as the reference calls it;
+    `normalize=True` maps x -> 2x - 1 first.  `valid` is accepted and ignored, as in the reference.
+
+    `weights` is anything `load_lpips_weights` takes (the package's state_dict, a torchvision backbone plus the
+    head file as (backbone, heads), lists, or file paths); none are shipped or downloaded, and weights=None
+    raises.  They are held as buffers, so .to(device) moves them.  Device tensors run the HIP plan
+    (ops.LPIPSPlan: prep, fp32 convs, max-pools and the per-layer kernel; forward only, so a device `pred` that
+    requires grad under enabled grad raises); CPU tensors run the torch restatement `lpips_value`, which
+    autograd differentiates.  Crops under 31 x 31 (alex) / 16 x 16 (vgg) raise ValueError."""
+
+    def __init__(self, boundary_ignore=None, type='alex', bgr2rgb=False, weights=None, normalize=False,
+                 per_image=False):
+        super().__init__()
+        _lpips_spec(type)
+        if weights is None:
+            raise ValueError("LPIPS: weights=None. No pretrained weights are shipped or downloaded: pass the `lpips` "
+                             "package's LPIPS(net=%r).state_dict() (or a file of it), a torchvision backbone "
+                             "state_dict with the package's head file as (backbone, heads), or (conv_weights, "
+                             "conv_biases, lins); generate_lpips_state_dict gives seeded stand-ins for tests" % type)
+        if isinstance(weights, dict) and 'conv_w' in weights and weights.get('net') == type:
+            w = weights
+        elif isinstance(weights, (tuple, list)) and len(weights) == 2:
+            w = load_lpips_weights(weights[0], type, heads=weights[1])
+        else:
+            w = load_lpips_weights(weights, type)
+        self.boundary_ignore = boundary_ignore
+        self.net = type
+        self.bgr2rgb = bgr2rgb
+        self.normalize = normalize
+        self.per_image = per_image
+        self.n_convs = len(w['conv_w'])
+        for i in range(self.n_convs):
+            self.register_buffer('conv%d_weight' % i, w['conv_w'][i].clone())
+            self.register_buffer('conv%d_bias' % i, w['conv_b'][i].clone())
+        for l in range(5):
+            self.register_buffer('lin%d' % l, w['lin'][l].clone())
+        self._plan = None
+
+    def weights(self):
+        return {'net': self.net, 'conv_w': [getattr(self, 'conv%d_weight' % i) for i in range(self.n_convs)],
+                'conv_b': [getattr(self, 'conv%d_bias' % i) for i in range(self.n_convs)],
+                'lin': [getattr(self, 'lin%d' % l) for l in range(5)]}
+
+    def plan(self):
+        """The HIP plan for the buffers' device (rebuilt if the module moved)."""
+        from . import ops
+        if self._plan is None or self._plan.device != self.lin0.device:
+            self._plan = ops.LPIPSPlan(self.weights())
+        return self._plan
+
+    def forward(self, pred, gt, valid=None):
+        if pred.dim() == 3:
+            pred, gt = pred.unsqueeze(0), gt.unsqueeze(0)
+        bi = self.boundary_ignore or 0
+        _lpips_check_crop(self.net, pred.shape[-2] - 2 * bi, pred.shape[-1] - 2 * bi)
+        if pred.is_cuda:
+            if torch.is_grad_enabled() and pred.requires_grad:
+                raise RuntimeError('LPIPS: the device path is forward-only (no HIP backward): a gradient to pred would '
+                                   'silently be zero.  Detach pred, or score CPU tensors for a differentiable value')
+            value = self.plan().forward(pred.detach().float(), gt.detach().float().to(pred.device), bi, self.bgr2rgb,
+                                        self.normalize)[0].clone()
+        else:
+            p, g = lpips_prepare(pred, gt, self.boundary_ignore, self.bgr2rgb)
+            value = lpips_value(p, g, self.weights(), self.normalize)[0]
+        return value if self.per_image else value.mean()
+
+
 # ------------------------------------------------------------------------------------------ harness
+
+def _lpips_column(lpips, boundary_ignore, what):
+    """The scorers' third column is an `LPIPS` module with the scorer's own crop."""
+    if lpips is None:
+        return None
+    if (getattr(lpips, 'boundary_ignore', None) or 0) != (boundary_ignore or 0):
+        raise ValueError('%s: lpips.boundary_ignore = %r, but the other columns are scored with %r'
+                         % (what, getattr(lpips, 'boundary_ignore', None), boundary_ignore))
+    return lpips
+
 
 def _batches(dataset, batch, burst_sz):
     for s in range(0, len(dataset), batch):
@@ -473,25 +781,31 @@ def _batches(dataset, batch, burst_sz):
         yield bursts, torch.stack([it[1] for it in items]), [it[2]['burst_name'] for it in items]
 
 
-def compute_score(net, dataset, boundary_ignore=40, burst_sz=None, device='cuda', batch=8, metrics=('psnr', 'ssim')):
+def compute_score(net, dataset, boundary_ignore=40, burst_sz=None, device='cuda', batch=8, metrics=('psnr', 'ssim'),
+                  lpips=None):
     """PSNR and SSIM columns of evaluation/synburst/compute_score.py:36-122 for one network: forward each
     burst, quantise like :109-111, per-image PSNR and SSIM with `boundary_ignore`, mean over the set.
     Bursts go through the engine `batch` at a time (bursts are independent); scores stay per image.
-    Returns {'psnr': mean, 'per_image': {burst_name: psnr}, 'ssim': mean, 'per_image_ssim': {burst_name: ssim}}
-    (LPIPS, the reference's third metric, is not computed).
+    Returns {'psnr': mean, 'per_image': {burst_name: psnr}, 'ssim': mean, 'per_image_ssim': {burst_name: ssim}}.
+
+    `lpips` is an `LPIPS` module built with the caller's weights and this `boundary_ignore` (moved to `device` by
+    the caller): the dict then gains 'lpips' (the mean) and 'per_image_lpips', the reference's third column,
+    computed per image on the quantised prediction.  'lpips' in `metrics` is accepted only together with it; without
+    a module it is an unknown metric, because there are no weights to compute it with.
 
     `metrics` may add 'msssim', the reference's MS-SSIM column: the dict then gains 'msssim' (the mean) and
     'per_image_msssim', computed per image on the quantised prediction with `boundary_ignore` like the other two.
     It is opt-in because MS-SSIM refuses crops under 32 x 32, which the other columns score, and because it is
     computed on the host (each quantised prediction is copied there; `MSSSIM` has no HIP kernel yet).  PSNR and
     SSIM are always reported."""
-    unknown = set(metrics) - {'psnr', 'ssim', 'msssim'}
+    unknown = set(metrics) - {'psnr', 'ssim', 'msssim'} - ({'lpips'} if lpips is not None else set())
     if unknown:
         raise ValueError('compute_score: unknown metrics %s' % sorted(unknown))
     psnr_fn = PSNR(boundary_ignore=boundary_ignore)
     ssim_fn = SSIM(boundary_ignore=boundary_ignore, use_for_loss=False)
     msssim_fn = MSSSIM(boundary_ignore=boundary_ignore, use_for_loss=False) if 'msssim' in metrics else None
-    per, per_ssim, per_ms = {}, {}, {}
+    lpips_fn = _lpips_column(lpips, boundary_ignore, 'compute_score')
+    per, per_ssim, per_ms, per_lp = {}, {}, {}, {}
     for bursts, gts, names in _batches(dataset, batch, burst_sz):
         with torch.no_grad():
             pred, _ = net(bursts.to(device))
@@ -502,10 +816,15 @@ def compute_score(net, dataset, boundary_ignore=40, burst_sz=None, device='cuda'
             per_ssim[name] = float(ssim_fn(pred[i:i + 1], gts[i:i + 1]))
             if msssim_fn is not None:
                 per_ms[name] = float(msssim_fn(pred[i:i + 1].cpu(), gts[i:i + 1].cpu()))   # host-side metric
+            if lpips_fn is not None:
+                with torch.no_grad():
+                    per_lp[name] = float(lpips_fn(pred[i:i + 1], gts[i:i + 1]))
     res = {'psnr': sum(per.values()) / max(1, len(per)), 'per_image': per,
            'ssim': sum(per_ssim.values()) / max(1, len(per_ssim)), 'per_image_ssim': per_ssim}
     if msssim_fn is not None:
         res.update(msssim=sum(per_ms.values()) / max(1, len(per_ms)), per_image_msssim=per_ms)
+    if lpips_fn is not None:
+        res.update(lpips=sum(per_lp.values()) / max(1, len(per_lp)), per_image_lpips=per_lp)
     return res
 
 

@@ -580,6 +580,219 @@ def ssim(pred, gt, valid=None, boundary_ignore=0, val_range=1.0):
 
 
 # ---------------------------------------------------------------------------------------------------
+# LPIPS (csrc/lpips.hip around dbsr_conv2d in fp32; dbsr_hip.h 'image-quality metrics')
+# ---------------------------------------------------------------------------------------------------
+LPIPS_NET_CODE = {'alex': 0, 'vgg': 1}
+
+
+def _f32_dev(what, *ts):
+    _need_cuda(*ts)
+    for t in ts:
+        if t.dtype != torch.float32:
+            raise ValueError('%s: tensors must be float32' % what)
+
+
+def lpips_prep(pred, gt, boundary_ignore=0, net='alex', bgr2rgb=False, normalize=False, out=None):
+    """dbsr_lpips_prep: pred, gt [B,3,H,W] fp32 NCHW -> [2B,Hc,Wc,8] fp32 NHWC (pred images first): crop, optional
+    channel flip, optional 2x - 1, (x - shift) / scale; channels 3..7 zero."""
+    _f32_dev('lpips_prep', pred, gt)
+    if pred.dim() != 4 or pred.shape[1] != 3 or gt.shape != pred.shape:
+        raise ValueError('lpips_prep: pred and gt must be [B, 3, H, W] of one shape')
+    B, _, H, W = pred.shape
+    bi = int(boundary_ignore or 0)
+    pred, gt = pred.contiguous(), gt.contiguous()
+    if out is None:
+        out = torch.empty(2 * B, max(H - 2 * bi, 0), max(W - 2 * bi, 0), 8, dtype=torch.float32, device=pred.device)
+    L.check(L.lib().dbsr_lpips_prep(B, H, W, bi, LPIPS_NET_CODE[net], int(bool(bgr2rgb)), int(bool(normalize)),
+                                    pred.data_ptr(), gt.data_ptr(), out.data_ptr(), L.stream_ptr(pred.device)),
+            'dbsr_lpips_prep')
+    return out
+
+
+def maxpool2d(x, k, s, out=None):
+    """dbsr_maxpool2d on an fp32 NHWC device tensor [N,H,W,C] (contiguous, C % 4 == 0): k x k / stride s, floor mode,
+    no padding -> [N,(H-k)//s+1,(W-k)//s+1,C]."""
+    _f32_dev('maxpool2d', x)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError('maxpool2d: x must be a contiguous [N, H, W, C] tensor')
+    N, H, W, C = x.shape
+    if out is None:
+        out = torch.empty(N, max((H - k) // s + 1, 0), max((W - k) // s + 1, 0), C, dtype=torch.float32,
+                          device=x.device)
+    L.check(L.lib().dbsr_maxpool2d(N, H, W, C, int(k), int(s), x.data_ptr(), C, out.data_ptr(), C,
+                                   L.stream_ptr(x.device)), 'dbsr_maxpool2d')
+    return out
+
+
+def lpips_layer(feat, lin, layer=0, want_map=False, per_layer=None, value=None, ws=None, dmap=None):
+    """dbsr_lpips_layer on one tapped feature tensor [2B,h,w,C] fp32 NHWC (pred images first) and lin [C]: returns
+    (value [B], per_layer [B,5], map [B,h,w] or None).  per_layer[:, layer] is this layer's mean distance; value is
+    set to it for layer 0 and has it added for layers 1..4 (pass the same per_layer / value for all five)."""
+    _f32_dev('lpips_layer', feat, lin)
+    if feat.dim() != 4 or feat.shape[0] % 2 or not feat.is_contiguous():
+        raise ValueError('lpips_layer: feat must be a contiguous [2B, h, w, C] tensor')
+    N, h, w, C = feat.shape
+    B = N // 2
+    if lin.numel() != C:
+        raise ValueError('lpips_layer: lin must hold C = %d weights' % C)
+    dev = feat.device
+    lin = lin.contiguous()
+    need = L.lib().dbsr_lpips_layer_workspace_bytes(B, h, w, C)
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    if per_layer is None:
+        per_layer = torch.zeros(B, 5, dtype=torch.float32, device=dev)
+    if value is None:
+        value = torch.zeros(B, dtype=torch.float32, device=dev)
+    if want_map and dmap is None:
+        dmap = torch.empty(B, h, w, dtype=torch.float32, device=dev)
+    L.check(L.lib().dbsr_lpips_layer(B, h, w, C, int(layer), feat.data_ptr(), lin.data_ptr(),
+                                     _ptr(dmap if want_map else None), per_layer.data_ptr(), value.data_ptr(),
+                                     ws.data_ptr(), need, L.stream_ptr(dev)), 'dbsr_lpips_layer')
+    return value, per_layer, (dmap if want_map else None)
+
+
+class LPIPSPlan:
+    """The whole LPIPS forward on the device for one set of weights (evaluation.load_lpips_weights' dict, tensors on
+    the HIP device): prep -> fp32 dbsr_conv2d with ReLU in the epilogue / dbsr_maxpool2d, NHWC with ld = C
+    throughout -> dbsr_lpips_layer at each of the five taps.  Weights are packed once; activations, workspaces
+    and results are allocated at the first call for a shape (B, H, W, boundary_ignore, want_maps) and reused, so
+    later calls for that shape allocate nothing and the sequence can be captured in a graph.  forward() returns
+    (value [B], per_layer [B,5], maps or None): views of the plan's buffers, overwritten by the next call.
+
+    Each conv runs per image pair and per block of K_CHANNELS input channels (see _build).  32 is where the
+    device's distance maps are as close to float64 as the float32 CPU restatement's ('LPIPS': at the
+    384 x 384 scoring shape VGG's deepest map is 5.8x the restatement's error unblocked, 3.3x at 128, 1.6x at 64,
+    1.2x at 32, for 2.9 / 3.4 / 4.0 / 5.5 ms)."""
+    K_CHANNELS = 32
+
+    def __init__(self, weights):
+        from .evaluation import LPIPS_NETS
+        self.net = weights['net']
+        self.spec = LPIPS_NETS[self.net]
+        self.device = weights['lin'][0].device
+        _need_cuda(*weights['conv_w'], *weights['conv_b'], *weights['lin'])
+        s = L.stream_ptr(self.device)
+        self.packed = []                                    # per conv: [(c0, n, packed weights, bias | None), ...]
+        for (cin, cout, k, _, _), w, b in zip(self.spec['convs'], weights['conv_w'], weights['conv_b']):
+            if tuple(w.shape) != (cout, cin, k, k) or tuple(b.shape) != (cout,):
+                raise ValueError('LPIPSPlan: conv %d -> %d has weights %s / bias %s' % (cin, cout, tuple(w.shape),
+                                                                                      tuple(b.shape)))
+            w32, b32 = w.detach().float().contiguous(), b.detach().float().contiguous()
+            slices = []
+            for c0 in range(0, cin, self.K_CHANNELS):
+                n = min(self.K_CHANNELS, cin - c0)
+                ws = w32[:, c0:c0 + n].contiguous()
+                wp = torch.empty(L.lib().dbsr_conv_packed_elems(cout, n, k, k), dtype=torch.float32, device=self.device)
+                bp = torch.empty(cout, dtype=torch.float32, device=self.device) if c0 == 0 else None
+                L.check(L.lib().dbsr_conv_pack_weights(ws.data_ptr(), b32.data_ptr() if c0 == 0 else None, cout, n, k,
+                                                       k, L.DBSR_F32, 1, wp.data_ptr(), _ptr(bp), s), 'pack')
+                slices.append((c0, n, wp, bp))
+            torch.cuda.current_stream(self.device).synchronize()      # the slices' host copies go out of scope
+            self.packed.append(slices)
+        self.lins = [v.detach().float().reshape(-1).contiguous() for v in weights['lin']]
+        self._shapes = {}
+
+    def _build(self, B, H, W, bi, want_maps):
+        """Buffers and the launch list for one shape."""
+        dev, f32 = self.device, torch.float32
+        h, w, c = H - 2 * bi, W - 2 * bi, 8
+        x = torch.empty(2 * B, h, w, c, dtype=f32, device=dev)
+        st = {'x0': x, 'steps': [], 'per_layer': torch.zeros(B, 5, dtype=f32, device=dev),
+              'value': torch.zeros(B, dtype=f32, device=dev), 'maps': [] if want_maps else None}
+        layer = 0
+        for op in self.spec['program']:
+            if isinstance(op, int):
+                cin, cout, k, s, p = self.spec['convs'][op]
+                oh, ow = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
+                y = torch.empty(2 * B, oh, ow, cout, dtype=f32, device=dev)
+                # One launch per image pair (frames b and B + b through the frame map): dbsr_conv2d picks its tile
+                # and split-K from the total pixel count, so a conv over the whole batch would round an image's
+                # features differently at B = 3 than at B = 1.  Two frames per launch is the B = 1 dispatch.
+                # K is summed in blocks of K_CHANNELS input channels, one launch per block, each block's result
+                # riding in as the next one's residual (bias in the first, ReLU after the last): the kernels'
+                # K-ordered fp32 chain over all of 9 x 512 non-negative products drifts several times further from
+                # the float64 value than a blocked sum does (DESIGN.md, 'LPIPS').
+                slices = self.packed[op]
+                part = [torch.empty_like(y) for _ in range(min(2, len(slices) - 1))]
+                descs = []
+                for b in range(B):
+                    for i, (c0, n, wp, bp) in enumerate(slices):
+                        last = i == len(slices) - 1
+                        d = L.ConvDesc()
+                        d.n_frames = 2
+                        d.x = L.tensor_desc(x, c, c0=c0, fmap=(1, B, b, 1))
+                        d.in_h, d.in_w, d.cin = h, w, n
+                        d.w, d.bias = wp.data_ptr(), _ptr(bp)
+                        d.cout, d.kh, d.kw, d.stride, d.pad, d.dil = cout, k, k, s, p, 1
+                        d.y = L.tensor_desc(y if last else part[i % 2], cout, fmap=(1, B, b, 1))
+                        d.out_h, d.out_w = oh, ow
+                        d.res = L.tensor_desc(part[(i - 1) % 2], cout, fmap=(1, B, b, 1)) if i else L.NULL_TENSOR
+                        if len(slices) == 1:
+                            d.act, d.post_act = L.ACT_RELU, L.ACT_NONE
+                        else:
+                            d.act, d.post_act = L.ACT_NONE, (L.ACT_RELU if last else L.ACT_NONE)
+                        d.out_mode, d.shuffle = L.OUT_NHWC, 0
+                        d.workspace_bytes = L.lib().dbsr_conv_workspace_bytes(d)
+                        descs.append(d)
+                # the launches run in stream order and share one split-K workspace
+                ws = torch.zeros(max(max(d.workspace_bytes for d in descs) // 4, 1), dtype=f32, device=dev)
+                for d in descs:
+                    d.workspace = ws.data_ptr()
+                st['steps'].append(('conv', descs, (x, y, ws, part)))
+                x, h, w, c = y, oh, ow, cout
+            elif op == 'tap':
+                need = L.lib().dbsr_lpips_layer_workspace_bytes(B, h, w, c)
+                if need == 0:
+                    raise L.DBSRLibError('lpips: tap %d of shape [%d, %d, %d, %d] is refused' % (layer, 2 * B, h, w, c))
+                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                dmap = torch.empty(B, h, w, dtype=f32, device=dev) if want_maps else None
+                if want_maps:
+                    st['maps'].append(dmap)
+                st['steps'].append(('tap', (B, h, w, c, layer, need), (x, ws, dmap)))
+                layer += 1
+            else:
+                _, k, s = op
+                y = torch.empty(2 * B, (h - k) // s + 1, (w - k) // s + 1, c, dtype=f32, device=dev)
+                st['steps'].append(('pool', (2 * B, h, w, c, k, s), (x, y)))
+                x, h, w = y, y.shape[1], y.shape[2]
+        return st
+
+    def forward(self, pred, gt, boundary_ignore=0, bgr2rgb=False, normalize=False, want_maps=False):
+        _f32_dev('lpips', pred, gt)
+        if pred.dim() != 4 or pred.shape[1] != 3 or gt.shape != pred.shape:
+            raise ValueError('lpips: pred and gt must be [B, 3, H, W] of one shape')
+        if pred.device != self.device or gt.device != self.device:
+            raise ValueError('lpips: the images are on %s, the weights on %s' % (pred.device, self.device))
+        B, _, H, W = pred.shape
+        bi = int(boundary_ignore or 0)
+        need = self.spec['min_side']
+        if H - 2 * bi < need or W - 2 * bi < need:
+            raise ValueError('lpips (%s): the crop %d x %d is smaller than %d x %d (the last pool needs a row)'
+                             % (self.net, H - 2 * bi, W - 2 * bi, need, need))
+        key = (B, H, W, bi, bool(want_maps))
+        st = self._shapes.get(key)
+        if st is None:
+            st = self._shapes[key] = self._build(B, H, W, bi, want_maps)
+        lib, s = L.lib(), L.stream_ptr(self.device)
+        lpips_prep(pred, gt, bi, self.net, bgr2rgb, normalize, out=st['x0'])
+        for kind, a, bufs in st['steps']:
+            if kind == 'conv':
+                for d in a:
+                    L.check(lib.dbsr_conv2d(d, s), 'dbsr_conv2d (lpips)')
+            elif kind == 'pool':
+                N, h, w, c, k, ps = a
+                L.check(lib.dbsr_maxpool2d(N, h, w, c, k, ps, bufs[0].data_ptr(), c, bufs[1].data_ptr(), c, s),
+                        'dbsr_maxpool2d')
+            else:
+                Bn, h, w, c, layer, need = a
+                L.check(lib.dbsr_lpips_layer(Bn, h, w, c, layer, bufs[0].data_ptr(), self.lins[layer].data_ptr(),
+                                             _ptr(bufs[2]), st['per_layer'].data_ptr(), st['value'].data_ptr(),
+                                             bufs[1].data_ptr(), need, s), 'dbsr_lpips_layer')
+        return st['value'], st['per_layer'], st['maps']
+
+
+# ---------------------------------------------------------------------------------------------------
 # synthetic training data (csrc/synth_ops.hip; dbsr_hip.h 'synthetic training data')
 # ---------------------------------------------------------------------------------------------------
 def _cam_params(params, B, what):

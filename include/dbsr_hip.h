@@ -466,6 +466,32 @@ int dbsr_ssim_backward(int B, int C, int H, int W, int boundary_ignore, const fl
                        const unsigned char* valid, float val_range, const float* scale, float* gpred, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* LPIPS (the `lpips` package's v0.1 metric as image_quality_v2.LPIPS calls it, image_quality_v2.py:139-163) around
+ * dbsr_conv2d in fp32: the input preparation, the backbone's max-pools and the per-layer distance.  fp32, NHWC,
+ * stream-ordered, no host read, no float atomics; two runs are bitwise equal.  Weights come from the caller.
+ *
+ * dbsr_lpips_prep: pred, gt [B][3][H][W] NCHW -> out [2B][Hc][Wc][8] NHWC, images 0..B-1 pred and B..2B-1 gt,
+ *   Hc = H - 2 boundary_ignore (likewise Wc): the crop, the optional channel flip [2,1,0], the optional 2x - 1,
+ *   then (x - shift) / scale per channel (a division; shift -.030 -.088 -.188, scale .458 .448 .450).  Channels
+ *   3..7 are written as zeros.  net picks the smallest crop side: 31 (alex), 16 (vgg).
+ * dbsr_maxpool2d: y [N][oh][ow][ldy] = max over k x k windows, stride s, of x [N][H][W][ldx], channels [0, C);
+ *   floor mode, no padding: oh = (H - k) / s + 1.  C, ldx, ldy multiples of 4; k, s in 1..8.  NaN propagates.
+ * dbsr_lpips_layer: feat [2B][h][w][C] (ld = C; C in 64, 128, 192, 256, 384, 512), lin [C]:
+ *   d[b][y][x]   = sum_c lin[c] (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2, f0 / f1 the pixel's vectors of
+ *                  images b / B + b, |.| the L2 norm over channels; written to map [B][h][w] unless map is NULL
+ *   per_layer[b][layer] (B x 5 floats) = mean over y, x of d[b]
+ *   value[b]     = (layer == 0 ? 0 : value[b]) + per_layer[b][layer]: call with layer = 0..4 in order
+ *   Per-block partial sums go to `workspace` (>= dbsr_lpips_layer_workspace_bytes, 0 for sizes the call refuses)
+ *   and one block adds them in a fixed order.  An image's value does not depend on the rest of the batch. */
+#define DBSR_LPIPS_ALEX 0
+#define DBSR_LPIPS_VGG 1
+int dbsr_lpips_prep(int B, int H, int W, int boundary_ignore, int net, int bgr2rgb, int normalize, const float* pred,
+                    const float* gt, float* out, void* stream);
+int dbsr_maxpool2d(int N, int H, int W, int C, int k, int s, const float* x, int ldx, float* y, int ldy, void* stream);
+size_t dbsr_lpips_layer_workspace_bytes(int B, int h, int w, int C);
+int dbsr_lpips_layer(int B, int h, int w, int C, int layer, const float* feat, const float* lin, float* map,
+                     float* per_layer, float* value, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------- synthetic training data (exports added under ABI 23: nothing existing changed) ----------------
  * The reference's rgb2rawburst (data/synthetic_burst_generation.py:23-246 over data/camera_pipeline.py) and its
  * inverse for viewing, process_linear_image_rgb (data/postprocessing_functions.py:32-50).  fp32, stream-ordered,
