@@ -1364,9 +1364,10 @@ struct WsCfg {
     static_assert((STAGE_U4 + W_PIECES * 64 + WM / 4) * 16 <= 160 * 1024, "weight staging must fit the LDS");
 };
 
+// The tile-at-a-time body (every wave runs all its rows' k-steps, then the whole block its epilogue): the WM = 32
+// tiles (64 x 8).  The WM = 64 tiles run ws_rows_body below.
 template <typename T, int WM, int TW, int TH, int NCH, int EPI>
-__global__ __launch_bounds__(512, 1) void conv3x3_ws_kernel(ConvK k, int tiles_x, int tiles_y, int nct, int nsp,
-                                                            int px) {
+__device__ __forceinline__ void ws_tile_body(const ConvK& k, int tiles_x, int tiles_y, int nct, int nsp, int px) {
     using C = WsCfg<WM, TW, TH, NCH>;
     static_assert(EPI >= 0 && EPI <= 5 && EPI != 4, "epilogues 0-3, 5");
     DBSR_OWN_SIMDS();
@@ -1635,6 +1636,276 @@ __global__ __launch_bounds__(512, 1) void conv3x3_ws_kernel(ConvK k, int tiles_x
     PIPE_STAMP(1);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Row-rolling body of the weight-stationary kernel for the 64-cout tiles (16 x 16 and 16 x 8 pixels; geometry and
+// schedule: ws_sched.hpp).  Block -> work, wave roles (wave (wc, wp): couts 32wc .. 32wc + 31 x tile rows RPW wp ..),
+// the halo image, the weight staging and each output's arithmetic are those of the tile body above: one in-order
+// fp32 MFMA chain over k-step = chunk x 9 + tap from zero, then bias, act, residual, post-act, gate.
+// What differs is the order of the work inside a tile.  Chunk by chunk a wave walks its RPW + 2 halo rows: the
+// B-fragment of (chunk, halo row i, kx) is read once (inline-asm ds_read_b128, AHEAD fragments before use, a
+// counted lgkmcnt per fragment) and feeds rows y = i - ky with tap 3 ky + kx, in both 16-cout blocks -- 36 reads
+// for 144 MFMAs at 16 x 16, cin 64, where the tile body reads 72.  Row y is final after halo row y + 2 of the
+// last chunk: its epilogue and 16-byte store run there, under the MFMAs of the rows below it; the residual is a
+// direct 16-byte buffer load per lane (the frame's resource: a partial cout tile's run past the last pixel reads
+// zeros), issued RES_LEAD reads earlier and pinned to the epilogue; the store is a buffer store whose lanes past cout
+// take an out-of-range offset, so it is issued unconditionally and the compiler's counted residual waits leave it
+// in flight.  The next tile's DMA pieces all precede the
+// tile's first load and store, so the tile barrier waits only until RPW operations -- this tile's stores -- are
+// left in flight.
+// ------------------------------------------------------------------------------------------------
+template <typename T, int TH, int NCH, int EPI>
+__device__ __forceinline__ void ws_rows_body(const ConvK& k, int tiles_x, int tiles_y, int nct, int nsp, int px) {
+    using S = wsr::Sched<TH, NCH>;
+    constexpr int TW = wsr::TW, WM = wsr::WM, RPW = S::RPW, NW = wsr::NW, AHEAD = wsr::AHEAD;
+    static_assert(EPI >= 0 && EPI <= 5 && EPI != 4, "epilogues 0-3, 5");
+    DBSR_OWN_SIMDS();
+    constexpr bool RT = EPI == 0 || EPI == 5, has_gate = EPI == 5;
+    __shared__ __attribute__((aligned(16))) u32x4_t lds[S::LDS_U4 + WM / 4];
+    float* lbias = (float*)(lds + S::LDS_U4);              // the cout tile's bias (fp32), read once after the staging
+
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = lane >> 4, col = lane & 15;
+    const int wc = wave % wsr::WC, wp = wave / wsr::WC;
+    const bool has_res = EPI == 2 || (RT && k.r != nullptr);
+    auto act1 = [&](float v) {
+        if constexpr (EPI == 1) return fmaxf(v, 0.f);
+        else if constexpr (RT) return apply_act(v, k.act);
+        else return v;
+    };
+    auto act2 = [&](float v) {
+        if constexpr (EPI == 2) return fmaxf(v, 0.f);
+        else if constexpr (RT) return apply_act(v, k.post_act);
+        else return v;
+    };
+
+    // block -> (cout tile, spatial stream); grid = 8 * px, px a multiple of nct
+    const int b = blockIdx.x, slot = b >> 3, spx = px / nct;
+    const int ct = slot % nct, SS = 8 * spx, sid = (b & 7) * spx + slot / nct;
+    const int my_tiles = sid < nsp ? (nsp - sid + SS - 1) / SS : 0;
+    if (my_tiles == 0) return;
+    PIPE_STAMP(0);
+
+    // the cout tile's weights (chunk-major copy: contiguous 1-KiB pieces) into the staging region
+    const int cb = ct * WM + wc * 32;
+    {
+        const __amdgpu_buffer_rsrc_t w_rsrc = buf_rsrc(k.w_pipe, 0xffffffffu);
+        const int p0 = (ct * WM >> 4) * NCH * 9;
+#pragma unroll
+        for (int it = 0; it < S::W_PER; ++it) {
+            const int piece = min(wave + NW * it, S::W_PIECES - 1);
+            blds16(w_rsrc, lane * 16, (p0 + piece) * 1024, lds + S::STAGE_U4 + piece * 64);
+        }
+    }
+    // lanes of a partial cout tile past cout compute and load but never store
+    const bool cout_ok = cb + 8 * g < k.cout;
+    if (threadIdx.x < WM) {             // ordered before its read by the staging barrier
+        const int co = ct * WM + threadIdx.x;
+        lbias[threadIdx.x] = (k.bias && co < k.cout) ? k.bias[co] : 0.f;
+    }
+
+    struct Tile { const T* xf; long long y_off, r_off, g_off; int y0, x0; };
+    auto decode = [&](int i) {
+        int L = sid + i * SS;
+        const int tx = L % tiles_x; L /= tiles_x;
+        const int ty = L % tiles_y;
+        const int f = L / tiles_y;
+        Tile t;
+        t.y0 = ty * TH; t.x0 = tx * TW;
+        t.xf = (const T*)k.x + map_frame(k.xm, f) * k.x_is;
+        const long long pix = (long long)t.y0 * k.out_w + t.x0;
+        t.y_off = map_frame(k.ym, f) * k.y_is + k.y_c0 + cb + pix * k.y_ld;
+        t.r_off = has_res ? map_frame(k.rm, f) * k.r_is : 0;   // residual frame base (buffer-resource base)
+        t.g_off = has_gate ? map_frame(k.gm, f) * k.g_is + k.g_c0 + cb + pix * k.g_ld : 0;
+        return t;
+    };
+    // this lane's pixel of the wave's first row, relative to the tile origin; rows follow at one frame row each
+    const long long lpix = (long long)wp * RPW * k.out_w + col;
+    const int ys = ((int)lpix * k.y_ld + 8 * g) * (int)sizeof(T), ys_row = k.out_w * k.y_ld * (int)sizeof(T);
+    const long long gl = has_gate ? lpix * k.g_ld + (ws_lane_ch(ct * WM, wc, g, k.cout) - cb) : 0;
+    const long long g_row = (long long)k.out_w * k.g_ld;
+    // residual: byte offsets inside the frame's resource, which spans the frame from its first channel, so the run
+    // of a partial cout tile past the frame's last pixel falls outside it (zeros) rather than past the allocation
+    const unsigned rframe_bytes = (unsigned)((long long)k.out_h * k.out_w * k.r_ld * (int)sizeof(T));
+    const int rl = has_res ? ((int)lpix * k.r_ld + k.r_c0 + cb + 8 * g) * (int)sizeof(T) : 0;
+    const int r_row = k.out_w * k.r_ld * (int)sizeof(T);
+
+    // halo DMA: piece `it` of this wave is item wave + 8 it (clamped: surplus slots rewrite the last piece with
+    // identical bytes); lane -> (halo pixel, physical k-group slot), tile-invariant
+    const int pix_b = k.x_ld * (int)sizeof(T);
+    const unsigned frame_bytes = (unsigned)((long long)k.in_h * k.in_w * pix_b);
+    const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) u32x4_t*)lds;
+    // (a piece starts at a multiple of 16 pixels, so the swizzle parity (p >> 2) & 1 and with it the lane's k-group
+    // are the same in every piece; the piece's chunk is wave-uniform.  Only (row, column) is kept per piece and
+    // the byte offset formed at every issue: the registers go to the weights)
+    const int kg16 = 16 * wsr::piece_kgroup(lane >> 2, lane & 3);
+    int h_rc[S::PER];
+#pragma unroll
+    for (int it = 0; it < S::PER; ++it) {
+        const int item = min(wave + NW * it, S::ITEMS - 1);
+        const int ii = item % S::IN_ITEMS;
+        const int p = ii * 16 + (lane >> 2);
+        const int r = p / S::HW, cc = p - r * S::HW;
+        h_rc[it] = p < S::NQ ? (r << 16) | cc : 0x7fff7fff;   // pixel slots past the halo land zeros
+    }
+    auto dma = [&](int it, const Tile& t, int buf) {
+        const int item = min(wave + NW * it, S::ITEMS - 1);
+        const int r = h_rc[it] >> 16, cc = h_rc[it] & 0xffff;
+        const int hy = t.y0 - 1 + r, hx = t.x0 - 1 + cc;
+        const bool ok = (unsigned)hy < (unsigned)k.in_h && (unsigned)hx < (unsigned)k.in_w;
+        const int off = (hy * k.in_w + hx) * pix_b + (item / S::IN_ITEMS) * 64 + kg16;
+        lds_dma16(t.xf, frame_bytes, ok ? off : BUF_OOB, 0, lds0 + (unsigned)((buf * S::STAGE_U4 + item * 64) * 16));
+    };
+    // B-fragment reads: byte address of halo pixel P0 + rho, k-group g (frag_slot), rho = pixel offset & 7, in the
+    // halo buffer of the current tile (moved to the other buffer after every tile)
+    const int P0 = wp * RPW * S::HW + col;
+    unsigned ba[8];
+#pragma unroll
+    for (int rho = 0; rho < 8; ++rho) ba[rho] = lds0 + 16u * (4 * P0 + wsr::frag_slot(P0 + rho, g));
+
+    Tile cur = decode(0);
+#pragma unroll
+    for (int it = 0; it < S::PER; ++it) dma(it, cur, 0);
+    // the wave's A-fragments of both 16-cout blocks for every (chunk, tap), from the staged weights; the loop's
+    // first barrier then orders these reads before any wave's DMA into the staging region
+    dma_barrier();
+    Frag<T> wr[NCH][9][2];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                wr[c][tap][h].v = __builtin_bit_cast(
+                    bf16x8_t, lds[S::STAGE_U4 + (((wc * 2 + h) * NCH + c) * 9 + tap) * 64 + lane]);
+    // this lane's 8 couts: accumulator r of 16-cout block h is cout cb + 8 g + 4 h + r
+    const f32x4_t bias0 = *(const f32x4_t*)(lbias + wc * 32 + 8 * g);
+    const f32x4_t bias1 = *(const f32x4_t*)(lbias + wc * 32 + 8 * g + 4);
+
+    PIPE_STAMP(2);
+    for (int ti = 0; ti < my_tiles; ++ti) {
+        PIPE_STAMP(3 + ti * 5);
+        // this wave's DMA pieces of tile ti landed: they are older than every load and store of tile ti - 1, so its
+        // youngest RPW vector-memory operations (that tile's stores) may stay in flight; then everyone's
+        DBSR_VM_WAIT(S::STORES);
+        PIPE_STAMP(4 + ti * 5);
+        __syncthreads();
+        PIPE_STAMP(5 + ti * 5);
+        PIPE_STAMP(6 + ti * 5);
+        const bool more = ti + 1 < my_tiles;
+        const Tile nxt = more ? decode(ti + 1) : cur;
+        const int buf = ti & 1;
+        const int r_tile = has_res ? (cur.y0 * k.out_w + cur.x0) * k.r_ld * (int)sizeof(T) + rl : 0;
+        // the tile's output rows as a buffer resource at the tile's origin (launch check: its 32-bit offsets)
+        const __amdgpu_buffer_rsrc_t y_rsrc = buf_rsrc((T*)k.y + cur.y_off, 0x7fffffffu);
+        f32x4_t acc[2][RPW];
+        u32x4_t resv[RPW], gatev[has_gate ? RPW : 1];
+        Frag<T> bq[AHEAD];
+        auto rd = [&](auto n_) {
+            constexpr int n = decltype(n_)::value, c = S::read_chunk(n), imm = S::read_pix(n);
+            // (asm operands name this lambda's own locals: clang does not capture for asm operands)
+            const unsigned a = ba[imm & 7];
+            bf16x8_t v;
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(a), "i"(16 * (c * S::CH_U4 + 4 * imm)));
+            bq[n % AHEAD].v = v;
+        };
+        // row y of this wave: bias, act, residual, post-act, gate, pack, one 16-B store
+        auto epilogue = [&](auto y_) {
+            constexpr int y = decltype(y_)::value;
+            // the loaded residual and gate are first touched here, behind this position's fragment wait: without the
+            // pin the compiler converts them right behind their loads and the stream waits out the memory latency
+            if (has_res) asm volatile("" : "+v"(resv[y]));
+            if constexpr (has_gate) asm volatile("" : "+v"(gatev[y]));
+            float v[8];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                v[r] = act1(acc[0][y][r] + bias0[r]);
+                v[4 + r] = act1(acc[1][y][r] + bias1[r]);
+            }
+            if (has_res) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[2 * e] = act2(v[2 * e] + H16<T>::lo(resv[y][e]));
+                    v[2 * e + 1] = act2(v[2 * e + 1] + H16<T>::hi(resv[y][e]));
+                }
+            }
+            if constexpr (has_gate) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[2 * e] = H16<T>::lo(gatev[y][e]) > 0.f ? v[2 * e] : 0.f;
+                    v[2 * e + 1] = H16<T>::hi(gatev[y][e]) > 0.f ? v[2 * e + 1] : 0.f;
+                }
+            }
+            u32x4_t o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = H16<T>::pack(v[2 * e], v[2 * e + 1]);
+            // a buffer store over the tile's own resource, lanes past cout at an out-of-range offset (dropped): a
+            // predicated store is a branch on an empty exec, and the compiler, no longer sure the store is issued,
+            // sized the next row's residual wait to cover it -- every row then waited out the store before it
+            __builtin_amdgcn_raw_buffer_store_b128(o, y_rsrc, cout_ok ? ys + y * ys_row : BUF_OOB, 0, 0);
+        };
+
+        StaticFor<0, AHEAD>::run([&](auto n_) { rd(n_); });
+        StaticFor<0, S::READS>::run([&](auto n_) {
+            constexpr int n = decltype(n_)::value, c = S::read_chunk(n);
+            // reads issued after read n: n + 1 .. n + AHEAD - 1
+            constexpr int newer = AHEAD - 1 < S::READS - 1 - n ? AHEAD - 1 : S::READS - 1 - n;
+            bf16x8_t v = bq[n % AHEAD].v;
+            asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "i"(newer));
+            Frag<T> bf;
+            bf.v = v;
+            StaticFor<0, 3>::run([&](auto ky_) {
+                constexpr int ky = decltype(ky_)::value;
+                if constexpr (S::feeds(n, ky)) {
+                    constexpr int y = S::read_row(n) - ky, tap = 3 * ky + S::read_kx(n);
+                    const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
+                    acc[0][y] = mma(wr[c][tap][0], bf, S::kstep(n, ky) == 0 ? z : acc[0][y]);
+                    acc[1][y] = mma(wr[c][tap][1], bf, S::kstep(n, ky) == 0 ? z : acc[1][y]);
+                }
+            });
+            if constexpr (n + AHEAD < S::READS) rd(std::integral_constant<int, n + AHEAD>{});
+            // side work at its stream position: the next tile's halo pieces, residual and gate loads, epilogues
+            StaticFor<0, S::PER>::run([&](auto it_) {
+                constexpr int it = decltype(it_)::value;
+                if constexpr (n == S::dma_at(it)) {
+                    if (more) dma(it, nxt, buf ^ 1);
+                }
+            });
+            StaticFor<0, RPW>::run([&](auto y_) {
+                constexpr int y = decltype(y_)::value;
+                if constexpr (n == S::res_at(y)) {
+                    if (has_res)
+                        resv[y] = __builtin_amdgcn_raw_buffer_load_b128(
+                            buf_rsrc((const T*)k.r + cur.r_off, rframe_bytes), r_tile + y * r_row, 0, 0);
+                    if constexpr (has_gate)
+                        gatev[y] = *(const u32x4_t*)((const T*)k.gt + cur.g_off + gl + y * g_row);
+                }
+                if constexpr (n == S::row_done(y)) epilogue(y_);
+            });
+        });
+        PIPE_STAMP(7 + ti * 5);
+        cur = nxt;
+#pragma unroll
+        for (int rho = 0; rho < 8; ++rho)
+            ba[rho] += buf ? (unsigned)(-S::STAGE_U4 * 16) : (unsigned)(S::STAGE_U4 * 16);
+    }
+    vm_drain();                         // (no LDS-DMA outstanding at s_endpgm: tools/isa_audit.py)
+    PIPE_STAMP(1);
+}
+
+template <typename T, int WM, int TW, int TH, int NCH, int EPI>
+__global__ __launch_bounds__(512, 1) void conv3x3_ws_kernel(ConvK k, int tiles_x, int tiles_y, int nct, int nsp,
+                                                            int px) {
+    // the run-time epilogues (0, and 5 with the gate) of the 16 x 16 tile at two chunks spill 14 and 20 VGPRs in the
+    // row-rolling body (144 weight registers + 32 accumulators + the activations' selects): they keep the tile body
+    constexpr bool rows = WM == wsr::WM && !(TH == 16 && NCH == 2 && (EPI == 0 || EPI == 5));
+    if constexpr (rows) {
+        static_assert(TW == wsr::TW, "the 64-cout tiles are 16 pixels wide");
+        ws_rows_body<T, TH, NCH, EPI>(k, tiles_x, tiles_y, nct, nsp, px);
+    } else {
+        ws_tile_body<T, WM, TW, TH, NCH, EPI>(k, tiles_x, tiles_y, nct, nsp, px);
+    }
+}
+
 int g_ws_enabled = 1;
 // weight-stationary kernel for `d` (blocks per XCD, 0: not applicable): 16-bit 3x3/s1/p1/d1 with
 // either 16 < cin <= 64, 32 < cout <= 512 on 16x16 tiles (WM 64) or 16 < cin <= 32, 16 <= cout <= 32 on 64x8
@@ -1666,6 +1937,7 @@ int pick_ws(const dbsr_conv_desc* d, const dbsr_conv_desc* g = nullptr) {
     if (d->out_w % tw || d->out_h % th) return 0;
     if ((long long)d->in_h * d->in_w * d->x.ld * 2 >= (1LL << 31)) return 0;   // 32-bit buffer offsets per frame
     if (d->res.ptr && (long long)d->out_h * d->out_w * d->res.ld * 2 >= (1LL << 31)) return 0;
+    if (!narrow && 16LL * d->out_w * d->y.ld * 2 >= (1LL << 31)) return 0;   // 32-bit store offsets per tile
     const int nct = (d->cout + wm - 1) / wm;
     const long long nsp = (long long)d->n_frames * (d->out_w / tw) * (d->out_h / th);
     const int cus = d->max_blocks > 0 ? std::min(d->max_blocks, num_cus()) : num_cus();

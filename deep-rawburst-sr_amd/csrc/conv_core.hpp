@@ -3,6 +3,7 @@
 #pragma once
 #include "common.hpp"
 #include "ks128_sched.hpp"
+#include "ws_sched.hpp"
 
 #include <vector>
 
