@@ -224,6 +224,12 @@ def lib():
             'dbsr_lpips_layer_workspace_bytes': ([c_int, c_int, c_int, c_int], c_size_t),
             'dbsr_lpips_layer': ([c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+            'dbsr_lpips_layer_backward': ([c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                           c_void_p], c_int),
+            'dbsr_maxpool2d_backward': ([c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_void_p], c_int),
+            'dbsr_lpips_stem_backward': ([c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p], c_int),
             'dbsr_unprocess_rgb': ([c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
             'dbsr_burst_synth': ([c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p], c_int),
@@ -264,6 +270,7 @@ EXPORTED = ['dbsr_abi_version', 'dbsr_last_error', 'dbsr_conv_packed_elems', 'db
             'dbsr_aligned_l1_workspace_bytes', 'dbsr_aligned_l1_forward', 'dbsr_aligned_l1_backward',
             'dbsr_ssim_workspace_bytes', 'dbsr_ssim_forward', 'dbsr_ssim_backward',
             'dbsr_lpips_prep', 'dbsr_maxpool2d', 'dbsr_lpips_layer_workspace_bytes', 'dbsr_lpips_layer',
+            'dbsr_lpips_layer_backward', 'dbsr_maxpool2d_backward', 'dbsr_lpips_stem_backward',
             'dbsr_unprocess_rgb', 'dbsr_burst_synth', 'dbsr_postprocess_rgb']
 
 

@@ -24,7 +24,8 @@ Host-side Python only: the network forward is the HIP path; PSNR runs as torch o
 the predictions live on; SSIM on device tensors runs the HIP kernels of csrc/metrics.hip (forward and
 gradient), on CPU tensors a torch restatement of the reference arithmetic.  MS-SSIM is host-side only: a
 torch restatement on CPU tensors.  LPIPS on device tensors runs the HIP plan of ops.LPIPSPlan (csrc/lpips.hip
-and the fp32 convs; forward only), on CPU tensors a torch restatement.
+and the fp32 convs; with differentiable=True also its HIP backward, csrc/lpips_grad.hip), on CPU tensors a torch
+restatement.
 """
 import math
 import os
@@ -690,6 +691,106 @@ def lpips_value(pred, gt, weights, normalize=False):
     return value, per_layer, maps
 
 
+def lpips_layer_grad(f0, f1, lin, gmap):
+    """The closed form dbsr_lpips_layer_backward computes, in f0's dtype: d(sum gmap * lpips_layer_map(f0, f1, lin))
+    / d f0 for [B, C, h, w] features and gmap [B, h, w] (or broadcastable).  With r = |f0|, D = r + eps, u = f0 / r
+    and g = 2 gmap lin (f0 / D - n(f1)): (g - u (u . g) r / D) / D.  At f0 = 0, u = 0: the limit g / eps
+    (dn/df = I / eps), which a finite difference confirms and where autograd gives NaN."""
+    r = f0.pow(2).sum(dim=1, keepdim=True).sqrt()
+    D = r + LPIPS_EPS
+    n1 = f1 / (f1.pow(2).sum(dim=1, keepdim=True).sqrt() + LPIPS_EPS)
+    g = 2 * gmap.to(f0).reshape(f0.shape[0], 1, *f0.shape[2:]) * lin.to(f0).view(1, -1, 1, 1) * (f0 / D - n1)
+    u = torch.where(r > 0, f0 / torch.where(r > 0, r, torch.ones_like(r)), torch.zeros_like(f0))
+    return (g - u * (u * g).sum(dim=1, keepdim=True) * (r / D)) / D
+
+
+def lpips_gates(x, weights, normalize=False):
+    """The ReLU masks and pool arg-max indices of the restatement's own forward on prepared images x [N,3,h,w]:
+    ([mask per conv: bool [N,C,h,w]], [arg-max per pool: int64 [N,C,oh,ow], flat index into the pool's h*w input,
+    first maximum in row-major window order])."""
+    spec = _lpips_spec(weights['net'])
+    if normalize:
+        x = 2 * x - 1
+    shift = torch.tensor(LPIPS_SHIFT, dtype=torch.float32).to(x).view(1, 3, 1, 1)
+    scale = torch.tensor(LPIPS_SCALE, dtype=torch.float32).to(x).view(1, 3, 1, 1)
+    x = (x - shift) / scale
+    masks, argmax = [], []
+    for op in spec['program']:
+        if isinstance(op, int):
+            _, _, _, s, p = spec['convs'][op]
+            x = F.relu(F.conv2d(x, weights['conv_w'][op].to(x), weights['conv_b'][op].to(x), stride=s, padding=p))
+            masks.append(x > 0)
+        elif op != 'tap':
+            x, idx = F.max_pool2d(x, op[1], op[2], return_indices=True)
+            argmax.append(idx)
+    return masks, argmax
+
+
+def lpips_backward_reference(pred, gt, weights, masks=None, argmax=None, normalize=False, gvalue=None):
+    """The gated backward of `lpips_value` on the host, in pred's dtype: (value [B], d(sum_b gvalue[b] value[b]) /
+    d pred) for prepared (flipped, cropped) [B,3,h,w] images.  The forward is the restatement, but each ReLU passes
+    where `masks` says so (one bool [B,C,h,w] per conv, for the pred images) and each max-pool takes the element
+    `argmax` names (int64 [B,C,oh,ow] per pool, flat index into the pool's h*w input).  A pre-activation within
+    rounding of zero, or two window elements within rounding of each other, may gate differently in another
+    precision; with the gates of the run under test this is the gradient of the function that run computed.
+    None: the forward's own gates, and the result is then autograd's gradient of `lpips_value`.  The gt half runs
+    the plain restatement.  The per-layer distance takes the closed form `lpips_layer_grad` (finite at an all-zero
+    pred vector)."""
+    spec = _lpips_spec(weights['net'])
+    B = pred.shape[0]
+    if masks is None or argmax is None:
+        own = lpips_gates(pred.detach(), weights, normalize)
+        masks = own[0] if masks is None else masks
+        argmax = own[1] if argmax is None else argmax
+    with torch.no_grad():
+        taps1 = lpips_features(gt.detach().to(pred.dtype), weights, normalize)
+    x = pred.detach().clone().requires_grad_(True)
+    leaf = x
+    if normalize:
+        x = 2 * x - 1
+    shift = torch.tensor(LPIPS_SHIFT, dtype=torch.float32).to(x).view(1, 3, 1, 1)
+    scale = torch.tensor(LPIPS_SCALE, dtype=torch.float32).to(x).view(1, 3, 1, 1)
+    x = (x - shift) / scale
+    taps0, ci, pi = [], 0, 0
+    for op in spec['program']:
+        if isinstance(op, int):
+            _, _, _, s, p = spec['convs'][op]
+            x = F.conv2d(x, weights['conv_w'][op].to(x), weights['conv_b'][op].to(x), stride=s, padding=p)
+            x = x * masks[ci].to(x)
+            ci += 1
+        elif op == 'tap':
+            taps0.append(x)
+        else:
+            idx = argmax[pi]
+            x = x.flatten(2).gather(2, idx.flatten(2)).view(idx.shape)
+            pi += 1
+    gv = torch.ones(B, dtype=pred.dtype) if gvalue is None else gvalue.to(pred.dtype)
+    value, grads = None, []
+    for f0, f1, lin in zip(taps0, taps1, weights['lin']):
+        f0d = f0.detach()
+        m = lpips_layer_map(f0d, f1, lin).mean(dim=(1, 2))
+        value = m if value is None else value + m
+        hw = f0.shape[2] * f0.shape[3]
+        grads.append(lpips_layer_grad(f0d, f1, lin, (gv / hw).view(B, 1, 1).expand(B, *f0.shape[2:])))
+    torch.autograd.backward(taps0, grads)
+    return value, leaf.grad
+
+
+class _LPIPSDevice(torch.autograd.Function):
+    """value [B] of ops.LPIPSPlan.forward with plan.backward as its gradient to pred."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, plan, bi, bgr2rgb, normalize):
+        value = plan.forward(pred.detach().float(), gt.detach().float().to(pred.device), bi, bgr2rgb, normalize)[0]
+        ctx.plan, ctx.token, ctx.dtype = plan, plan.token(), pred.dtype
+        return value.clone()
+
+    @staticmethod
+    def backward(ctx, gvalue):
+        gpred = ctx.plan.backward(gvalue.float().contiguous(), token=ctx.token)
+        return gpred.to(ctx.dtype, copy=True), None, None, None, None, None
+
+
 class LPIPS(nn.Module):
     """models/loss/image_quality_v2.py:139-163 over lpips.LPIPS(net=type) (v0.1, spatial=False), restated: the
     optional channel flip [2,1,0], the boundary crop, the metric, the mean over the batch (`per_image`: [B]
@@ -699,12 +800,18 @@ class LPIPS(nn.Module):
     `weights` is anything `load_lpips_weights` takes (the package's state_dict, a torchvision backbone plus the
     head file as (backbone, heads), lists, or file paths); none are shipped or downloaded, and weights=None
     raises.  They are held as buffers, so .to(device) moves them.  Device tensors run the HIP plan
-    (ops.LPIPSPlan: prep, fp32 convs, max-pools and the per-layer kernel; forward only, so a device `pred` that
-    requires grad under enabled grad raises); CPU tensors run the torch restatement `lpips_value`, which
-    autograd differentiates.  Crops under 31 x 31 (alex) / 16 x 16 (vgg) raise ValueError."""
+    (ops.LPIPSPlan: prep, fp32 convs, max-pools and the per-layer kernel); CPU tensors run the torch restatement
+    `lpips_value`, which autograd differentiates.  Crops under 31 x 31 (alex) / 16 x 16 (vgg) raise ValueError.
+
+    `differentiable=True` makes the device value a training objective: a device `pred` that requires grad goes
+    through the plan's HIP backward (ops.LPIPSPlan.backward; the gradient reaches pred only -- gt.requires_grad
+    raises ValueError; one forward per backward for a shape, a backward after a newer forward raises RuntimeError).
+    At an all-zero feature vector of pred the gradient is the finite limit of the closed form, where the CPU path's
+    autograd gives NaN.  By default the device path is forward-only and such a `pred` under enabled grad raises.
+    CPU tensors ignore the flag."""
 
     def __init__(self, boundary_ignore=None, type='alex', bgr2rgb=False, weights=None, normalize=False,
-                 per_image=False):
+                 per_image=False, differentiable=False):
         super().__init__()
         _lpips_spec(type)
         if weights is None:
@@ -723,6 +830,7 @@ class LPIPS(nn.Module):
         self.bgr2rgb = bgr2rgb
         self.normalize = normalize
         self.per_image = per_image
+        self.differentiable = bool(differentiable)
         self.n_convs = len(w['conv_w'])
         for i in range(self.n_convs):
             self.register_buffer('conv%d_weight' % i, w['conv_w'][i].clone())
@@ -749,9 +857,15 @@ class LPIPS(nn.Module):
         bi = self.boundary_ignore or 0
         _lpips_check_crop(self.net, pred.shape[-2] - 2 * bi, pred.shape[-1] - 2 * bi)
         if pred.is_cuda:
+            if self.differentiable and torch.is_grad_enabled() and gt.requires_grad:
+                raise ValueError('LPIPS: gt.requires_grad on the device -- the HIP backward reaches pred only; detach gt')
+            if self.differentiable and torch.is_grad_enabled() and pred.requires_grad:
+                value = _LPIPSDevice.apply(pred, gt, self.plan(), bi, self.bgr2rgb, self.normalize)
+                return value if self.per_image else value.mean()
             if torch.is_grad_enabled() and pred.requires_grad:
                 raise RuntimeError('LPIPS: the device path is forward-only (no HIP backward): a gradient to pred would '
-                                   'silently be zero.  Detach pred, or score CPU tensors for a differentiable value')
+                                   'silently be zero.  Detach pred, score CPU tensors, or build the module with '
+                                   'differentiable=True for the HIP backward')
             value = self.plan().forward(pred.detach().float(), gt.detach().float().to(pred.device), bi, self.bgr2rgb,
                                         self.normalize)[0].clone()
         else:

@@ -654,6 +654,137 @@ def lpips_layer(feat, lin, layer=0, want_map=False, per_layer=None, value=None, 
     return value, per_layer, (dmap if want_map else None)
 
 
+def lpips_layer_backward(feat, lin, gvalue=None, out=None, accumulate=False):
+    """dbsr_lpips_layer_backward: feat [2B,h,w,C] and lin as for lpips_layer, gvalue [B] the upstream gradient of
+    value (None: ones) -> d(sum_b gvalue[b] per_layer[b]) / d feat[:B] as [B,h,w,C], written to `out` or, with
+    accumulate, added to it.  At an all-zero pred vector it is the limit g / 1e-10 (finite), not autograd's NaN."""
+    _f32_dev('lpips_layer_backward', feat, lin)
+    if feat.dim() != 4 or feat.shape[0] % 2 or not feat.is_contiguous():
+        raise ValueError('lpips_layer_backward: feat must be a contiguous [2B, h, w, C] tensor')
+    N, h, w, C = feat.shape
+    B = N // 2
+    if lin.numel() != C:
+        raise ValueError('lpips_layer_backward: lin must hold C = %d weights' % C)
+    dev = feat.device
+    if gvalue is None:
+        gvalue = torch.ones(B, dtype=torch.float32, device=dev)
+    _f32_dev('lpips_layer_backward', gvalue)
+    if gvalue.numel() != B:
+        raise ValueError('lpips_layer_backward: gvalue must hold B = %d values' % B)
+    if out is None:
+        if accumulate:
+            raise ValueError('lpips_layer_backward: accumulate needs `out`')
+        out = torch.empty(B, h, w, C, dtype=torch.float32, device=dev)
+    _f32_dev('lpips_layer_backward', out)
+    if tuple(out.shape) != (B, h, w, C) or not out.is_contiguous():
+        raise ValueError('lpips_layer_backward: out must be a contiguous [B, h, w, C] tensor')
+    L.check(L.lib().dbsr_lpips_layer_backward(B, h, w, C, feat.data_ptr(), lin.contiguous().data_ptr(),
+                                              gvalue.contiguous().data_ptr(), out.data_ptr(), int(bool(accumulate)),
+                                              L.stream_ptr(dev)), 'dbsr_lpips_layer_backward')
+    return out
+
+
+def maxpool2d_backward(x, dy, k, s, out=None):
+    """dbsr_maxpool2d_backward: x [N,H,W,C] the pool's input, dy [N,oh,ow,C] -> dx [N,H,W,C], each element the sum of
+    dy over the windows whose first maximum it is; every element is written (k / s: 3 / 2 or 2 / 2)."""
+    _f32_dev('maxpool2d_backward', x, dy)
+    if x.dim() != 4 or not x.is_contiguous() or not dy.is_contiguous():
+        raise ValueError('maxpool2d_backward: x and dy must be contiguous [N, H, W, C] tensors')
+    N, H, W, C = x.shape
+    if tuple(dy.shape) != (N, (H - k) // s + 1, (W - k) // s + 1, C):
+        raise ValueError('maxpool2d_backward: dy %s does not belong to x %s' % (tuple(dy.shape), tuple(x.shape)))
+    if out is None:
+        out = torch.empty_like(x)
+    L.check(L.lib().dbsr_maxpool2d_backward(N, H, W, C, int(k), int(s), x.data_ptr(), dy.data_ptr(), out.data_ptr(),
+                                            L.stream_ptr(x.device)), 'dbsr_maxpool2d_backward')
+    return out
+
+
+def lpips_stem_backward(dy, w, shape, boundary_ignore=0, net='alex', bgr2rgb=False, normalize=False, out=None):
+    """dbsr_lpips_stem_backward: dy [B,oh,ow,64] (the gradient of the first conv's pre-activation) and that conv's
+    weights w [64,3,k,k] -> gpred of `shape` [B,3,H,W]: the conv's transpose and dbsr_lpips_prep's, every element
+    written (zeros in the boundary_ignore frame)."""
+    _f32_dev('lpips_stem_backward', dy, w)
+    B, _, H, W = shape
+    bi = int(boundary_ignore or 0)
+    k, s, p = (11, 4, 2) if net == 'alex' else (3, 1, 1)
+    oh, ow = (H - 2 * bi + 2 * p - k) // s + 1, (W - 2 * bi + 2 * p - k) // s + 1
+    if tuple(dy.shape) != (B, oh, ow, 64) or not dy.is_contiguous() or tuple(w.shape) != (64, 3, k, k):
+        raise ValueError('lpips_stem_backward (%s): dy must be [%d, %d, %d, 64] and w [64, 3, %d, %d]'
+                         % (net, B, oh, ow, k, k))
+    if out is None:
+        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=dy.device)
+    L.check(L.lib().dbsr_lpips_stem_backward(B, H, W, bi, LPIPS_NET_CODE[net], int(bool(bgr2rgb)), int(bool(normalize)),
+                                             dy.data_ptr(), w.contiguous().data_ptr(), out.data_ptr(),
+                                             L.stream_ptr(dy.device)), 'dbsr_lpips_stem_backward')
+    return out
+
+
+def _lpips_dgrad_pack(w, k_channels):
+    """A stride-1 backbone conv's weights [cout,cin,k,k] (fp32, device) -> the packed slices of its input-gradient
+    conv, which reads dy's cout channels in blocks of k_channels: [(c0, n, packed weights), ...].  The dgrad conv's
+    weights are the flipped transpose, wd[ci][co][ky][kx] = w[co][ci][k-1-ky][k-1-kx]."""
+    cout, cin, k, _ = w.shape
+    wd = w.detach().float().flip(2, 3).transpose(0, 1).contiguous()
+    s = L.stream_ptr(w.device)
+    slices = []
+    for c0 in range(0, cout, k_channels):
+        n = min(k_channels, cout - c0)
+        ws = wd[:, c0:c0 + n].contiguous()
+        wp = torch.empty(L.lib().dbsr_conv_packed_elems(cin, n, k, k), dtype=torch.float32, device=w.device)
+        L.check(L.lib().dbsr_conv_pack_weights(ws.data_ptr(), None, cin, n, k, k, L.DBSR_F32, 1, wp.data_ptr(), None,
+                                               s), 'pack (lpips dgrad)')
+        slices.append((c0, n, wp))
+    torch.cuda.current_stream(w.device).synchronize()                 # the slices' host copies go out of scope
+    return slices
+
+
+def _lpips_dgrad_descs(slices, dy, dx, part, B, h, w, cin, cout, k, p):
+    """The dbsr_conv2d launches of one stride-1 input gradient: dy [B,h,w,cout] -> dx [B,h,w,cin], per image (the
+    forward's rule: an image's rounding must not depend on its batch) and per block of dy's channels, each block's
+    result riding in as the next one's residual through part[0] / part[1].  Returns (descs, workspace)."""
+    descs = []
+    for b in range(B):
+        for i, (c0, n, wp) in enumerate(slices):
+            last = i == len(slices) - 1
+            d = L.ConvDesc()
+            d.n_frames = 1
+            d.x = L.tensor_desc(dy, cout, c0=c0, fmap=(1, 1, b, 1))
+            d.in_h, d.in_w, d.cin = h, w, n
+            d.w, d.bias = wp.data_ptr(), None
+            d.cout, d.kh, d.kw, d.stride, d.pad, d.dil = cin, k, k, 1, k - 1 - p, 1
+            d.y = L.tensor_desc(dx if last else part[i % 2], cin, fmap=(1, 1, b, 1))
+            d.out_h, d.out_w = h, w
+            d.res = L.tensor_desc(part[(i - 1) % 2], cin, fmap=(1, 1, b, 1)) if i else L.NULL_TENSOR
+            d.act, d.post_act = L.ACT_NONE, L.ACT_NONE
+            d.out_mode, d.shuffle = L.OUT_NHWC, 0
+            d.workspace_bytes = L.lib().dbsr_conv_workspace_bytes(d)
+            descs.append(d)
+    ws = torch.zeros(max(max(d.workspace_bytes for d in descs) // 4, 1), dtype=torch.float32, device=dy.device)
+    for d in descs:
+        d.workspace = ws.data_ptr()
+    return descs, ws
+
+
+def lpips_conv_dgrad(dy, w, padding, k_channels=None):
+    """The input gradient of a stride-1 backbone conv exactly as LPIPSPlan.backward launches it: dy [B,h,w,cout]
+    fp32 NHWC and the conv's weights w [cout,cin,k,k] -> dx [B,h,w,cin] (2 * padding == k - 1)."""
+    _f32_dev('lpips_conv_dgrad', dy, w)
+    B, h, wd_, cout = dy.shape
+    cin, k = w.shape[1], w.shape[2]
+    if w.shape[0] != cout or 2 * padding != k - 1 or not dy.is_contiguous():
+        raise ValueError('lpips_conv_dgrad: dy [B,h,w,cout] contiguous, w [cout,cin,k,k], 2 * padding == k - 1')
+    slices = _lpips_dgrad_pack(w, k_channels or LPIPSPlan.K_CHANNELS)
+    dx = torch.empty(B, h, wd_, cin, dtype=torch.float32, device=dy.device)
+    part = [torch.empty_like(dx) for _ in range(min(2, len(slices) - 1))]
+    descs, ws = _lpips_dgrad_descs(slices, dy, dx, part, B, h, wd_, cin, cout, k, padding)
+    s = L.stream_ptr(dy.device)
+    for d in descs:
+        L.check(L.lib().dbsr_conv2d(d, s), 'dbsr_conv2d (lpips dgrad)')
+    torch.cuda.current_stream(dy.device).synchronize()                # ws and part go out of scope
+    return dx
+
+
 class LPIPSPlan:
     """The whole LPIPS forward on the device for one set of weights (evaluation.load_lpips_weights' dict, tensors on
     the HIP device): prep -> fp32 dbsr_conv2d with ReLU in the epilogue / dbsr_maxpool2d, NHWC with ld = C
@@ -661,6 +792,9 @@ class LPIPSPlan:
     and results are allocated at the first call for a shape (B, H, W, boundary_ignore, want_maps) and reused, so
     later calls for that shape allocate nothing and the sequence can be captured in a graph.  forward() returns
     (value [B], per_layer [B,5], maps or None): views of the plan's buffers, overwritten by the next call.
+    backward() is the gradient of the last forward's value with respect to pred (csrc/lpips_grad.hip and the
+    convs' input gradients through dbsr_conv2d; DESIGN.md, 'LPIPS as a training objective'); its weights and
+    buffers are made at the first backward, so a plan that only scores pays nothing for it.
 
     Each conv runs per image pair and per block of K_CHANNELS input channels (see _build).  32 is where the
     device's distance maps are as close to float64 as the float32 CPU restatement's ('LPIPS': at the
@@ -694,6 +828,10 @@ class LPIPSPlan:
             self.packed.append(slices)
         self.lins = [v.detach().float().reshape(-1).contiguous() for v in weights['lin']]
         self._shapes = {}
+        # backward(): the convs' fp32 weights, from which the input-gradient convs are packed at the first backward
+        self._w32 = [w.detach().float().contiguous() for w in weights['conv_w']]
+        self._dgrad = None
+        self._last_key = None
 
     def _build(self, B, H, W, bi, want_maps):
         """Buffers and the launch list for one shape."""
@@ -741,7 +879,7 @@ class LPIPSPlan:
                 ws = torch.zeros(max(max(d.workspace_bytes for d in descs) // 4, 1), dtype=f32, device=dev)
                 for d in descs:
                     d.workspace = ws.data_ptr()
-                st['steps'].append(('conv', descs, (x, y, ws, part)))
+                st['steps'].append(('conv', descs, (x, y, ws, part, op)))
                 x, h, w, c = y, oh, ow, cout
             elif op == 'tap':
                 need = L.lib().dbsr_lpips_layer_workspace_bytes(B, h, w, c)
@@ -776,6 +914,9 @@ class LPIPSPlan:
         st = self._shapes.get(key)
         if st is None:
             st = self._shapes[key] = self._build(B, H, W, bi, want_maps)
+        st['gen'] = st.get('gen', 0) + 1                    # backward() belongs to this forward of the shape
+        st['args'] = (B, H, W, bi, bool(bgr2rgb), bool(normalize))
+        self._last_key = key
         lib, s = L.lib(), L.stream_ptr(self.device)
         lpips_prep(pred, gt, bi, self.net, bgr2rgb, normalize, out=st['x0'])
         for kind, a, bufs in st['steps']:
@@ -792,6 +933,114 @@ class LPIPSPlan:
                                              _ptr(bufs[2]), st['per_layer'].data_ptr(), st['value'].data_ptr(),
                                              bufs[1].data_ptr(), need, s), 'dbsr_lpips_layer')
         return st['value'], st['per_layer'], st['maps']
+
+    # ------------------------------------------------------------------------------------------ backward
+    def token(self):
+        """(shape key, generation) of the last forward: pass it to backward() to have a backward that no longer
+        belongs to the shape's newest forward refused instead of run on overwritten activations."""
+        if self._last_key is None:
+            raise RuntimeError('LPIPSPlan: no forward has run')
+        return self._last_key, self._shapes[self._last_key]['gen']
+
+    def activations(self, shape_key=None):
+        """The activations the last forward of `shape_key` (default: the last forward's) saved, in program order:
+        ('relu', y) per conv and ('pool', x, y) per max-pool, [2B,h,w,C] NHWC views of the plan's buffers with the
+        pred images first (what backward() gates and routes by)."""
+        st = self._shapes[shape_key or self.token()[0]]
+        out = []
+        for kind, _, bufs in st['steps']:
+            if kind == 'conv':
+                out.append(('relu', bufs[1]))
+            elif kind == 'pool':
+                out.append(('pool', bufs[0], bufs[1]))
+        return out
+
+    def _build_backward(self, st):
+        """Buffers and the launch list of the backward for one shape: the forward's steps in reverse.  Two flat
+        gradient buffers alternate (a conv's or pool's input gradient goes to the other one; a tap adds into the
+        one that holds its activation's gradient; the ReLU gate runs in place), two more carry the K blocks."""
+        if self._dgrad is None:
+            self._dgrad = [None] + [_lpips_dgrad_pack(w, self.K_CHANNELS) for w in self._w32[1:]]
+        B, H, W, bi = st['args'][:4]
+        dev, f32 = self.device, torch.float32
+        sizes = [B * b[1].shape[1] * b[1].shape[2] * b[1].shape[3] for k, _, b in st['steps'] if k != 'tap']
+        flat = [torch.empty(max(sizes), dtype=f32, device=dev) for _ in range(4)]
+        view = lambda i, h, w, c: flat[i][:B * h * w * c].view(B, h, w, c)
+        bw = {'gpred': torch.empty(B, 3, H, W, dtype=f32, device=dev), 'ones': torch.ones(B, dtype=f32, device=dev),
+              'gvalue': torch.ones(B, dtype=f32, device=dev), 'flat': flat, 'launches': []}
+        cur, have = 0, False                               # the buffer of the current activation's gradient
+        for kind, a, bufs in reversed(st['steps']):
+            if kind == 'tap':
+                _, h, w, c, layer, _ = a
+                bw['launches'].append(('layer', (B, h, w, c, layer, int(have)), (bufs[0], view(cur, h, w, c))))
+                have = True
+            elif kind == 'pool':
+                _, h, w, c, k, s = a
+                oh, ow = bufs[1].shape[1], bufs[1].shape[2]
+                bw['launches'].append(('pool', (B, h, w, c, k, s), (bufs[0], view(cur, oh, ow, c),
+                                                                   view(cur ^ 1, h, w, c))))
+                cur ^= 1
+            else:
+                x, y, op = bufs[0], bufs[1], bufs[4]
+                cin, cout, k, _, p = self.spec['convs'][op]
+                oh, ow = y.shape[1], y.shape[2]
+                dy = view(cur, oh, ow, cout)
+                bw['launches'].append(('gate', (B, oh * ow, cout), (L.tensor_desc(dy, cout), L.tensor_desc(y, cout))))
+                if op == 0:
+                    bw['launches'].append(('stem', None, (dy,)))
+                else:
+                    h, w = x.shape[1], x.shape[2]
+                    dx = view(cur ^ 1, h, w, cin)
+                    part = [view(2, h, w, cin), view(3, h, w, cin)]
+                    descs, ws = _lpips_dgrad_descs(self._dgrad[op], dy, dx, part, B, h, w, cin, cout, k, p)
+                    bw['launches'].append(('conv', descs, (dy, dx, ws, part)))
+                    cur ^= 1
+        return bw
+
+    def backward(self, gvalue=None, token=None):
+        """d(sum_b gvalue[b] value[b]) / d pred of the last forward() (of `token`'s shape when given), fp32
+        [B,3,H,W]: a view of the plan's buffer, overwritten by the next backward of that shape.  gvalue: [B] device
+        tensor, None = ones.  With `token` (from token() right after the forward) a backward that no longer belongs
+        to the shape's newest forward raises RuntimeError: the saved activations are gone."""
+        key, gen = token if token is not None else self.token()
+        st = self._shapes[key]
+        if st['gen'] != gen:
+            raise RuntimeError('LPIPSPlan: backward() after another forward of the same shape -- the saved '
+                               'activations are gone (one forward per backward)')
+        bw = st.get('bwd')
+        if bw is None:
+            bw = st['bwd'] = self._build_backward(st)
+        B, H, W, bi, bgr2rgb, normalize = st['args']
+        if gvalue is None:
+            gv = bw['ones']
+        else:
+            if gvalue.device != self.device or gvalue.numel() != B:
+                raise ValueError('lpips backward: gvalue must hold B = %d values on %s' % (B, self.device))
+            gv = bw['gvalue']
+            gv.copy_(gvalue.detach().reshape(-1))
+        lib, s = L.lib(), L.stream_ptr(self.device)
+        for kind, a, bufs in bw['launches']:
+            if kind == 'layer':
+                Bn, h, w, c, layer, acc = a
+                L.check(lib.dbsr_lpips_layer_backward(Bn, h, w, c, bufs[0].data_ptr(), self.lins[layer].data_ptr(),
+                                                      gv.data_ptr(), bufs[1].data_ptr(), acc, s),
+                        'dbsr_lpips_layer_backward')
+            elif kind == 'pool':
+                Bn, h, w, c, k, ps = a
+                L.check(lib.dbsr_maxpool2d_backward(Bn, h, w, c, k, ps, bufs[0].data_ptr(), bufs[1].data_ptr(),
+                                                    bufs[2].data_ptr(), s), 'dbsr_maxpool2d_backward')
+            elif kind == 'gate':
+                Bn, hw, c = a
+                L.check(lib.dbsr_act_backward(Bn, hw, c, L.ACT_RELU, bufs[0], bufs[1], bufs[0], s),
+                        'dbsr_act_backward (lpips)')
+            elif kind == 'conv':
+                for d in a:
+                    L.check(lib.dbsr_conv2d(d, s), 'dbsr_conv2d (lpips dgrad)')
+            else:
+                L.check(lib.dbsr_lpips_stem_backward(B, H, W, bi, LPIPS_NET_CODE[self.net], int(bgr2rgb),
+                                                     int(normalize), bufs[0].data_ptr(), self._w32[0].data_ptr(),
+                                                     bw['gpred'].data_ptr(), s), 'dbsr_lpips_stem_backward')
+        return bw['gpred']
 
 
 # ---------------------------------------------------------------------------------------------------

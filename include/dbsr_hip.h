@@ -492,6 +492,33 @@ size_t dbsr_lpips_layer_workspace_bytes(int B, int h, int w, int C);
 int dbsr_lpips_layer(int B, int h, int w, int C, int layer, const float* feat, const float* lin, float* map,
                      float* per_layer, float* value, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The gradient of LPIPS with respect to pred (csrc/lpips_grad.hip; exports added under ABI 23).  fp32, NHWC with
+ * ld = C, stream-ordered, no host read, no atomics (owner-computes gathers in a fixed order: two runs are bitwise
+ * equal), no workspace.  Only the pred half (frames 0..B-1) gets a gradient; gt and every weight are constants.
+ * The stride-1 convs between these calls take their input gradients from dbsr_conv2d (ops.LPIPSPlan.backward).
+ *
+ * dbsr_lpips_layer_backward: feat [2B][h][w][C] and lin [C] as for dbsr_lpips_layer, gvalue [B] (device) the
+ *   upstream gradient of value[b]; gfeat [B][h][w][C] (=, or += with accumulate != 0) d(gvalue[b] per_layer[b])/df0:
+ *   with r = |f0|, D = r + 1e-10, u = f0 / r and g_c = 2 gvalue[b] / (h w) lin[c] (f0_c / D - f1_c / (|f1| + 1e-10)),
+ *     gfeat_j = (g_j - u_j (u . g) r / D) / D.
+ *   At f0 = 0 it is the limit g_j / 1e-10 (dn/df = I / eps): finite, and what a float64 finite difference gives,
+ *   where torch autograd returns NaN.
+ * dbsr_maxpool2d_backward: x [N][H][W][C] the pool's saved input, dy [N][oh][ow][C]; dx [N][H][W][C] = for each
+ *   input element the sum of dy over the windows whose arg-max it is (first maximum in row-major window order, as
+ *   torch), zero for elements no window selects or floor mode drops; every element is written.  k / s: 3 / 2 or
+ *   2 / 2; C a multiple of 4.
+ * dbsr_lpips_stem_backward: the first conv's input gradient and the transpose of dbsr_lpips_prep in one pass.
+ *   dy [B][oh][ow][64] = the gradient of the first conv's pre-activation (ReLU-gated), w [64][3][k][k] that conv's
+ *   weights in torch layout (alex: k 11, stride 4, pad 2; vgg: k 3, stride 1, pad 1; oh = (Hc + 2 pad - k) / stride
+ *   + 1); gpred [B][3][H][W] NCHW, every element written: zeros in the boundary_ignore frame, inside it the conv's
+ *   transpose times 2 (normalize) divided by the channel's scale, at the flipped channel when bgr2rgb. */
+int dbsr_lpips_layer_backward(int B, int h, int w, int C, const float* feat, const float* lin, const float* gvalue,
+                              float* gfeat, int accumulate, void* stream);
+int dbsr_maxpool2d_backward(int N, int H, int W, int C, int k, int s, const float* x, const float* dy, float* dx,
+                            void* stream);
+int dbsr_lpips_stem_backward(int B, int H, int W, int boundary_ignore, int net, int bgr2rgb, int normalize,
+                             const float* dy, const float* w, float* gpred, void* stream);
+
 /* ---------------- synthetic training data (exports added under ABI 23: nothing existing changed) ----------------
  * The reference's rgb2rawburst (data/synthetic_burst_generation.py:23-246 over data/camera_pipeline.py) and its
  * inverse for viewing, process_linear_image_rgb (data/postprocessing_functions.py:32-50).  fp32, stream-ordered,
