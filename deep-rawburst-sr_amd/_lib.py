@@ -20,6 +20,8 @@ SRC_F32_NCHW, SRC_U8_NHWC = 0, 1
 POST_GAINS, POST_CCM, POST_GAMMA, POST_SMOOTHSTEP = 1, 2, 4, 8
 # loss-scale state buffer (dbsr_hip.h DBSR_LS_*): 32-bit word indices and the buffer's length in words
 LS_SCALE, LS_GROWTH_TRACKER, LS_FOUND_INF, LS_ADAM_STEP, LS_SKIPPED, LS_WORDS = 0, 1, 2, 3, 4, 8
+# PixelWiseError's metrics (dbsr_hip.h DBSR_METRIC_*)
+METRIC_CODES = {'l1': 0, 'l2': 1, 'l2_sqrt': 2, 'charbonnier': 3}
 
 
 class FrameMap(ctypes.Structure):
@@ -181,6 +183,14 @@ def lib():
             'dbsr_adam_step_guarded': ([c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float,
                                         c_float, c_float, c_void_p, c_void_p], c_int),
             'dbsr_loss_scale_update': ([c_void_p, c_float, c_float, c_int, c_void_p], c_int),
+            'dbsr_objective_workspace_bytes': ([c_int, c_int, c_int], c_size_t),
+            'dbsr_objective_step': ([c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     Tensor, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+            'dbsr_objective_forward': ([c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+            'dbsr_psnr_from_stats': ([c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+            'dbsr_relu_grad_scaled': ([c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, Tensor, c_void_p],
+                                      c_int),
             'dbsr_dgrad_weights': ([c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p], c_int),
             'dbsr_conv_wgrad_sd_workspace_bytes': ([c_int, c_int, c_int, c_int, c_int, c_int], c_size_t),
             'dbsr_conv_wgrad_sd': ([c_int, c_int, c_int, Tensor, c_int, c_int, c_int, Tensor, c_int, c_int, c_int, c_int,
@@ -264,6 +274,8 @@ EXPORTED = ['dbsr_abi_version', 'dbsr_last_error', 'dbsr_conv_packed_elems', 'db
             'dbsr_dgrad_sd_pack', 'dbsr_conv_dgrad_sd', 'dbsr_act_backward', 'dbsr_flow_finalize_backward',
             'dbsr_l1_loss_backward_scaled', 'dbsr_grad_unscale_check', 'dbsr_adam_step_guarded',
             'dbsr_loss_scale_update',
+            'dbsr_objective_workspace_bytes', 'dbsr_objective_step', 'dbsr_objective_forward', 'dbsr_psnr_from_stats',
+            'dbsr_relu_grad_scaled',
             'dbsr_resize_bilinear', 'dbsr_gauss_reflect', 'dbsr_color_fit', 'dbsr_color_apply', 'dbsr_pwc_dense',
             'dbsr_pwc_dense_supported', 'dbsr_pwc_refine', 'dbsr_pwc_refine_supported', 'dbsr_pwc_extract',
             'dbsr_pwc_extract_supported', 'dbsr_pwc_level_prep', 'dbsr_pwc_level_prep_supported',

@@ -1191,3 +1191,101 @@ def loss_scale_update(state, growth_factor=2.0, backoff_factor=0.5, growth_inter
     L.check(L.lib().dbsr_loss_scale_update(state.data_ptr(), float(growth_factor), float(backoff_factor),
                                            int(growth_interval), L.stream_ptr(state.device)),
             'dbsr_loss_scale_update')
+
+
+# ---------------------------------------------------------------------------------------------------
+# objectives of the training step (csrc/objective.hip; dbsr_hip.h 'objectives of the training step')
+# ---------------------------------------------------------------------------------------------------
+def _objective_args(pred, gt, metric, boundary_ignore):
+    _need_cuda(pred, gt)
+    if pred.dim() != 4 or pred.shape[1] != 3 or gt.shape != pred.shape:
+        raise ValueError('objective: pred and gt must be [B, 3, H, W] of one shape')
+    if metric not in L.METRIC_CODES:
+        raise ValueError('objective: unknown metric %r (one of %s)' % (metric, ', '.join(L.METRIC_CODES)))
+    return _f32c(pred), _f32c(gt), L.METRIC_CODES[metric], int(boundary_ignore or 0)
+
+
+def objective_step(pred, gt, boundary_ignore, metric='l1', weight=1.0, gextra=None, state=None,
+                   dpre_dtype=torch.float32, ld=8):
+    """dbsr_objective_step on fp32 NCHW device tensors [B,3,H,W]: returns (loss [3] = {metric, weight * metric,
+    weight / count}, dpre [B,H,W,ld] of dpre_dtype = scale * [pred > 0] * (weight * dmetric/dpred + gextra) in the
+    crop, stats [B,2] float64 = {sum (pred - gt)^2, elements} per image).  state: a loss-scale state or None."""
+    pred, gt, code, bi = _objective_args(pred, gt, metric, boundary_ignore)
+    B, _, H, W = pred.shape
+    dev = pred.device
+    if gextra is not None:
+        _need_cuda(gextra)
+        if gextra.shape != pred.shape:
+            raise ValueError('objective_step: gextra must have pred\'s shape')
+        gextra = _f32c(gextra)
+    if state is not None:
+        _ls_check(state)
+    dpre = torch.zeros(B, H, W, ld, dtype=dpre_dtype, device=dev)
+    loss = torch.zeros(3, dtype=torch.float32, device=dev)
+    stats = torch.zeros(B, 2, dtype=torch.float64, device=dev)
+    need = L.lib().dbsr_objective_workspace_bytes(B, H, W)
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    L.check(L.lib().dbsr_objective_step(B, H, W, bi, code, float(weight), pred.data_ptr(), gt.data_ptr(), _ptr(gextra),
+                                        _ptr(state), L.tensor_desc(dpre, ld), loss.data_ptr(), stats.data_ptr(),
+                                        ws.data_ptr(), need, L.stream_ptr(dev)), 'dbsr_objective_step')
+    return loss, dpre, stats
+
+
+def objective_forward(pred, gt, boundary_ignore, metric='l1', weight=1.0, valid=None, want_grad=True):
+    """dbsr_objective_forward: returns (loss [3] = {metric, weight * metric, weight / denominator}, g [B,3,H,W] the
+    unnormalised gradient (dloss/dpred = loss[2] / weight * g) or None, stats [B,2] float64).  valid: [B,1,H,W]
+    mask, with 'l1' and 'l2' only (the reference's other two metrics cannot take one)."""
+    pred, gt, code, bi = _objective_args(pred, gt, metric, boundary_ignore)
+    B, _, H, W = pred.shape
+    dev = pred.device
+    v8 = None
+    if valid is not None:
+        if metric not in ('l1', 'l2'):
+            raise ValueError('objective: metric %r does not take a valid mask (l1 and l2 do)' % (metric,))
+        _need_cuda(valid)
+        if valid.numel() != B * H * W:
+            raise ValueError('objective: valid must be [B, 1, H, W]')
+        v8 = valid.to(torch.uint8).contiguous()
+    g = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev) if want_grad else None
+    loss = torch.zeros(3, dtype=torch.float32, device=dev)
+    stats = torch.zeros(B, 2, dtype=torch.float64, device=dev)
+    need = L.lib().dbsr_objective_workspace_bytes(B, H, W)
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    L.check(L.lib().dbsr_objective_forward(B, H, W, bi, code, float(weight), pred.data_ptr(), gt.data_ptr(), _ptr(v8),
+                                           _ptr(g), loss.data_ptr(), stats.data_ptr(), ws.data_ptr(), need,
+                                           L.stream_ptr(dev)), 'dbsr_objective_forward')
+    return loss, g, stats
+
+
+def psnr_from_stats(stats, max_value=1.0, max_values=None, masked=False):
+    """dbsr_psnr_from_stats: stats [B,2] float64 (objective_step / objective_forward) -> (psnr [1] = the mean over
+    the images whose PSNR is finite, 0 if none; per_image [B]).  max_values: per-image maxima [B] (device) instead
+    of the scalar max_value."""
+    _need_cuda(stats)
+    if stats.dtype != torch.float64 or stats.dim() != 2 or stats.shape[1] != 2 or not stats.is_contiguous():
+        raise ValueError('psnr_from_stats: stats must be a contiguous float64 [B, 2] tensor')
+    B = stats.shape[0]
+    dev = stats.device
+    if max_values is not None:
+        _need_cuda(max_values)
+        max_values = _f32c(max_values).reshape(-1)
+        if max_values.numel() != B:
+            raise ValueError('psnr_from_stats: max_values must hold B values')
+    out = torch.zeros(1, dtype=torch.float32, device=dev)
+    per = torch.zeros(B, dtype=torch.float32, device=dev)
+    L.check(L.lib().dbsr_psnr_from_stats(B, stats.data_ptr(), int(bool(masked)),
+                                         float(max_value if max_value is not None else 0.0), _ptr(max_values),
+                                         out.data_ptr(), per.data_ptr(), L.stream_ptr(dev)), 'dbsr_psnr_from_stats')
+    return out, per
+
+
+def relu_grad_scaled(pred, gout, state, dpre):
+    """dbsr_relu_grad_scaled: dpre [B,H,W,ld >= C] = state.scale * [pred > 0] * gout (pred / gout fp32 NCHW).
+    Returns dpre."""
+    _ls_check(state, pred, gout, dpre)
+    B, C, H, W = pred.shape
+    pred, gout = _f32c(pred), _f32c(gout)
+    L.check(L.lib().dbsr_relu_grad_scaled(B, C, H, W, pred.data_ptr(), gout.data_ptr(), state.data_ptr(),
+                                          L.tensor_desc(dpre, dpre.shape[-1]), L.stream_ptr(pred.device)),
+            'dbsr_relu_grad_scaled')
+    return dpre

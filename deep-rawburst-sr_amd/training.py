@@ -127,6 +127,16 @@ class DBSRTrainer:
     runs on a second flat buffer of them with the same lr, betas and eps; pwc_grad_view(p) is a PWC parameter's
     last gradient.  Not with loss_scale (so not fp16) and not with a world size above 1.  Without it such a net is
     refused.
+
+    objective: None keeps the built-in L1 plan, op for op.  A metric name ('l1', 'l2', 'l2_sqrt', 'charbonnier') or
+    an objectives.Objective makes the step's loss weight * metric + ssim * (1 - SSIM) + extra(pred, gt):
+    dbsr_objective_step takes the place of the l1_loss_bwd op, an SSIM term adds dbsr_ssim_forward / _backward ops
+    whose gradient it adds before the ReLU gate, and an `extra` callable (LPIPS with differentiable=True, any torch
+    objective) runs eagerly between the plan's forward and backward on a leaf over the plan's prediction, its
+    autograd gradient entering the same way.  Loss scaling, the bucketed all-reduce, graph replay and `flow=` work
+    as without; step returns the total loss and `last_stats` holds Loss/total, Loss/rgb, Loss/raw/rgb, Stat/psnr
+    and the extra terms as device tensors (the step reads nothing back).  A name takes the trainer's
+    boundary_ignore, an Objective its own.  Not with optimizer=False; `extra` not with alignment_grad=True.
     """
     # re-pack every conv's weights in one launch (dbsr_conv_pack_weights_batch, bitwise the per-conv
     # pack / dgrad-transpose / pack launches it replaces: False runs those, for A/B and the equality test)
@@ -137,12 +147,23 @@ class DBSRTrainer:
 
     def __init__(self, net, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, boundary_ignore=40, process_group=None,
                  bucket_bytes=4 << 20, optimizer=True, loss_scale=None, init_scale=65536.0, growth_factor=2.0,
-                 backoff_factor=0.5, growth_interval=2000, flow_grad=False, alignment_grad=False):
+                 backoff_factor=0.5, growth_interval=2000, flow_grad=False, alignment_grad=False, objective=None):
         dev = next(net.parameters()).device
         if dev.type != 'cuda':
             raise RuntimeError('DBSRTrainer needs the network on a HIP device')
         self.net, self.dev, self.dtype = net, dev, net.compute_dtype
         self.alignment_grad = bool(alignment_grad)
+        self.objective = None
+        if objective is not None:
+            from .objectives import Objective
+            if not optimizer:
+                raise ValueError('DBSRTrainer: objective= belongs to the fused step; with optimizer=False (the '
+                                 'autograd path) the caller computes the loss from the prediction')
+            self.objective = Objective.of(objective, boundary_ignore)
+            if self.objective.extra is not None and self.alignment_grad:
+                raise NotImplementedError('DBSRTrainer: an objective with an `extra` callable is not supported with '
+                                          'alignment_grad=True (both run eagerly around the plan)')
+            boundary_ignore = self.objective.boundary_ignore
         self.want_flow_grad = bool(flow_grad) or self.alignment_grad
         self._flow_plan = None            # the plan whose dflow buffer holds the last backward's dL/d(offsets)
         # Loss scaling (csrc/loss_scale.hip, torch.amp.GradScaler's rule on the device).  None: no scaling -- the
@@ -225,6 +246,13 @@ class DBSRTrainer:
         self.step_count = 0
         self.plans = {}
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        if self.objective is not None:
+            # dbsr_objective_step's {metric, weight * metric, weight / count}; the total is the weighted metric
+            # itself unless SSIM / extra terms are added to it after the plan (device arithmetic, nothing read back)
+            self._obj_loss = torch.zeros(3, dtype=torch.float32, device=dev)
+            if self.objective.ssim is None and self.objective.extra is None:
+                self.loss = self._obj_loss[1:2]
+            self._obj_plan = None
         self.use_graph = True         # step(): replay the plan as HIP graphs after its first (eager) run
         self._pack()
 
@@ -497,7 +525,39 @@ class DBSRTrainer:
         dP = NHWC(B, HS, WS, 8, dt, dev)
         nlb = (B * HS * WS + 255) // 256
         plan.fwd_end = len(plan.ops)            # ops[:fwd_end]: the forward with saved activations (+ grad zeroing)
-        if self.scaling:
+        obj = self.objective
+        if obj is not None:
+            # the objective's ops: [ssim_fwd, ssim_bwd,] <metric>_loss_bwd.  The SSIM gradient of ssim * (1 - SSIM)
+            # lands in `gextra` (its scale -ssim / (3 B Hm Wm + 1e-12) is a constant without a mask: a device scalar
+            # written once); an `extra` callable's gradient is added there eagerly, before plan.obj_op runs
+            gextra = None
+            if obj.ssim is not None or obj.extra is not None:
+                gextra = bufs['gextra'] = torch.zeros(B, 3, HS, WS, dtype=torch.float32, device=dev)
+            if obj.ssim is not None:
+                need = lib.dbsr_ssim_workspace_bytes(B, 3, HS, WS, self.bi)
+                if need == 0:
+                    raise ValueError('DBSRTrainer: the SSIM term needs a crop of at least 11 x 11 pixels, got %d x %d'
+                                     % (HS - 2 * self.bi, WS - 2 * self.bi))
+                sws = torch.zeros(need, dtype=torch.uint8, device=dev)
+                plan.ssim_result = torch.zeros(2, dtype=torch.float32, device=dev)
+                ssums = torch.zeros(B, 2, dtype=torch.float32, device=dev)
+                windows = 3.0 * B * (HS - 2 * self.bi - 10) * (WS - 2 * self.bi - 10)
+                sscale = torch.full((1,), -obj.ssim / (windows + 1e-12), dtype=torch.float32, device=dev)
+                plan.keep.extend([sws, ssums, sscale])
+                plan.add('ssim_fwd', lib.dbsr_ssim_forward, B, 3, HS, WS, self.bi, pred.data_ptr(),
+                         bufs['gt'].data_ptr(), None, obj.ssim_val_range, None, ssums.data_ptr(),
+                         plan.ssim_result.data_ptr(), sws.data_ptr(), need)
+                plan.add('ssim_bwd', lib.dbsr_ssim_backward, B, 3, HS, WS, self.bi, pred.data_ptr(),
+                         bufs['gt'].data_ptr(), None, obj.ssim_val_range, sscale.data_ptr(), gextra.data_ptr(), None, 0)
+            plan.obj_op = len(plan.ops)
+            plan.obj_stats = torch.zeros(B, 2, dtype=torch.float64, device=dev)
+            need = lib.dbsr_objective_workspace_bytes(B, HS, WS)
+            plan.add(obj.metric + '_loss_bwd', lib.dbsr_objective_step, B, HS, WS, self.bi, L.METRIC_CODES[obj.metric],
+                     obj.weight, pred.data_ptr(), bufs['gt'].data_ptr(),
+                     gextra.data_ptr() if gextra is not None else None,
+                     self._ls.data_ptr() if self.scaling else None, dP.d(0), self._obj_loss.data_ptr(),
+                     plan.obj_stats.data_ptr(), ws('obj', need), need)
+        elif self.scaling:
             # dP = scale * dL/dpre with the scale read from the scaler's state on the device (the loss stays unscaled)
             plan.add('l1_loss_bwd', lib.dbsr_l1_loss_backward_scaled, B, 3, HS, WS, self.bi, pred.data_ptr(),
                      bufs['gt'].data_ptr(), self._ls.data_ptr(), dP.d(0), self.loss.data_ptr(), ws('l1', 4 * nlb),
@@ -644,8 +704,11 @@ class DBSRTrainer:
         plan = self._load(burst, frame_gt, flow)
         stream = L.stream_ptr(self.dev)
         # segments of the op list between the gradient buckets' completion points: each segment is one HIP
-        # graph replay (after one eager step), and a bucket's all-reduce is issued right after its segment
-        cuts = [0] + ([b[0] for b in plan.buckets] if self.world > 1 else []) + [len(plan.ops)]
+        # graph replay (after one eager step), and a bucket's all-reduce is issued right after its segment.  An
+        # objective's `extra` callable runs eagerly before the objective's op: one more cut
+        eager_at = plan.obj_op if (self.objective is not None and self.objective.extra is not None) else None
+        cuts = [0] + ([eager_at] if eager_at is not None else []) + \
+            ([b[0] for b in plan.buckets] if self.world > 1 else []) + [len(plan.ops)]
         segs = [(a, b) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
         if self.use_graph and plan.graphs is None and plan.eager_runs > 0:
             plan.graphs = []
@@ -661,6 +724,8 @@ class DBSRTrainer:
                 plan.graphs[si].replay()
             else:
                 plan.run_list(plan.ops[a:b], stream)
+            if b == eager_at:
+                self._objective_extra(plan)
             while bi < len(plan.buckets) and plan.buckets[bi][0] == b:
                 if self.world > 1:
                     _, lo, hi = plan.buckets[bi]
@@ -669,8 +734,60 @@ class DBSRTrainer:
         plan.eager_runs += 1
         for w_ in works:
             w_.wait()
+        self._objective_total(plan)
         self._optimizer_step(stream)
         return self.loss.clone()          # (self.loss is the plan's buffer, overwritten by the next step)
+
+    def _objective_extra(self, plan):
+        """The objective's `extra` term on a leaf over the plan's prediction; its gradient goes into the plan's
+        gextra buffer (added to the SSIM term's when there is one), which the objective's op reads next."""
+        pred = plan.bufs['pred'].detach().requires_grad_(True)
+        with torch.enable_grad():
+            value = self.objective.extra(pred, plan.bufs['gt'])
+            (g,) = torch.autograd.grad(value, pred)
+        if self.objective.ssim is not None:
+            plan.bufs['gextra'].add_(g.to(torch.float32))
+        else:
+            plan.bufs['gextra'].copy_(g.to(torch.float32))
+        plan.extra_value = value.detach().to(torch.float32).reshape(1)
+
+    def _objective_total(self, plan):
+        """Loss/total of a step with an objective: the weighted metric plus the SSIM and extra terms, on the device."""
+        obj = self.objective
+        if obj is None:
+            return
+        self._obj_plan = plan
+        if obj.ssim is None and obj.extra is None:
+            return                                      # self.loss is the weighted metric's own buffer
+        total = self._obj_loss[1:2].clone()
+        if obj.ssim is not None:
+            total += obj.ssim * (1.0 - plan.ssim_result[:1])
+        if obj.extra is not None:
+            total += plan.extra_value
+        self.loss = total
+
+    @property
+    def last_stats(self):
+        """The reference actor's statistics of the last step with an objective (actors/dbsr_actors.py:35-45) as
+        device tensors of shape [1] -- Loss/total, Loss/rgb (weight * metric), Loss/raw/rgb, Stat/psnr, and
+        Loss/ssim, Loss/raw/ssim, Loss/extra for the terms the objective has; None before the first step or without
+        an objective.  Stat/psnr is one small launch here (dbsr_psnr_from_stats); nothing is read back."""
+        obj, plan = self.objective, getattr(self, '_obj_plan', None)
+        if obj is None or plan is None:
+            return None
+        st = {'Loss/total': self.loss.clone(), 'Loss/rgb': self._obj_loss[1:2].clone(),
+              'Loss/raw/rgb': self._obj_loss[0:1].clone()}
+        if obj.ssim is not None:
+            raw = 1.0 - plan.ssim_result[:1]
+            st['Loss/raw/ssim'], st['Loss/ssim'] = raw, obj.ssim * raw
+        if obj.extra is not None:
+            st['Loss/extra'] = plan.extra_value.clone()
+        if obj.psnr:
+            out = torch.zeros(1, dtype=torch.float32, device=self.dev)
+            L.check(L.lib().dbsr_psnr_from_stats(plan.obj_stats.shape[0], plan.obj_stats.data_ptr(), 0, 1.0, None,
+                                                 out.data_ptr(), None, L.stream_ptr(self.dev)), 'psnr_from_stats')
+            st['Stat/psnr'] = out
+        return st
 
     def _optimizer_step(self, stream):
         self.step_count += 1
@@ -703,7 +820,13 @@ class DBSRTrainer:
     def forward_backward(self, burst, frame_gt, flow=None):
         """Loss and gradients only (no all-reduce, no optimizer step): for tests."""
         plan = self._load(burst, frame_gt, flow)
-        plan.run(L.stream_ptr(self.dev))
+        if self.objective is not None and self.objective.extra is not None:
+            plan.run_list(plan.ops[:plan.obj_op], L.stream_ptr(self.dev))
+            self._objective_extra(plan)
+            plan.run_list(plan.ops[plan.obj_op:], L.stream_ptr(self.dev))
+        else:
+            plan.run(L.stream_ptr(self.dev))
+        self._objective_total(plan)
         self._unscale_only(L.stream_ptr(self.dev))
         return self.loss, plan.bufs['pred']
 
@@ -843,6 +966,9 @@ class DBSRRealWorldTrainer(DBSRTrainer):
             # op) and is not scaled yet: refuse before anything is allocated
             raise ValueError('DBSRRealWorldTrainer: train in torch.bfloat16 or torch.float32 (the aligned objective '
                              'has no loss scaling here)')
+        if kwargs.get('objective') is not None:
+            raise ValueError('DBSRRealWorldTrainer: the step\'s objective is the aligned L1 of the real-world recipe; '
+                             'objective= belongs to DBSRTrainer')
         if kwargs.get('alignment_grad'):
             raise NotImplementedError('DBSRRealWorldTrainer: alignment_grad=True is not supported (the real-world '
                                       'step has its own segments; train PWC-Net with DBSRTrainer)')

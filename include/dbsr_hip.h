@@ -707,6 +707,51 @@ int dbsr_adam_step_guarded(long long n, float* param, const float* grad, float* 
  * adam_step += 1, growth_tracker += 1 and, when it reaches growth_interval, scale *= growth_factor and
  * growth_tracker = 0.  Then found_inf = 0.  Factors > 0 (1, 1: a fixed scale), growth_interval >= 1. */
 int dbsr_loss_scale_update(void* state, float growth_factor, float backoff_factor, int growth_interval, void* stream);
+
+/* ---------------- objectives of the training step (csrc/objective.hip; exports added under ABI 23) ----------------
+ * PixelWiseError's metrics (models/loss/image_quality_v2.py:24-66) with their gradients, and PSNR (:69-101) from
+ * per-image statistics.  pred / gt / gextra / g: fp32 NCHW [B][3][H][W]; the crop drops boundary_ignore pixels on
+ * each side.  With d = pred - gt over the crop, count = B 3 Hc Wc (l2_sqrt: B Hc Wc):
+ *   metric       loss                              count * dloss/dpred
+ *   L1           mean |d|                          sign(d)
+ *   L2           mean d^2                          2 d
+ *   L2_SQRT      mean_pixels sqrt(sum_c d_c^2)     d_c / sqrt(sum_c d_c^2), 0 where that norm is 0 (torch: NaN)
+ *   CHARBONNIER  mean sqrt(d^2 + 1e-6)             d / sqrt(d^2 + 1e-6)
+ * No atomics; every sum goes through per-block partials in `workspace` and one finishing block in a fixed order
+ * (the per-image statistics and every loss but the step op's l1 in double): two runs are bitwise equal.  Nothing is
+ * read back.  workspace: >= dbsr_objective_workspace_bytes (one size serves both calls), 16-B aligned.
+ *
+ * dbsr_objective_step (generalises dbsr_l1_loss_backward and _scaled):
+ *   dpre   NHWC in the compute dtype, channels [c0, c0 + 3): S * [pred > 0] * (weight * dloss/dpred + gextra)
+ *          inside the crop, 0 outside; S = state's scale (state NULL: 1), gextra NULL: none.  Both layouts of
+ *          dbsr_l1_loss_backward: the generic one, and 16-bit with ld 8, c0 0 (one 16-B store per pixel, channels
+ *          3..7 zero; ptr 16-B aligned).  A product beyond the dtype's range is stored as inf.
+ *   loss   3 floats: {the metric, weight * the metric, weight / count}
+ *   stats  2 B doubles: {sum d^2, elements} of image b over the crop (PSNR's inputs)
+ *   With DBSR_METRIC_L1, weight 1 and gextra NULL, loss[0] and dpre are bitwise dbsr_l1_loss_backward's (state
+ *   NULL) and dbsr_l1_loss_backward_scaled's: for that the l1 loss keeps those kernels' float sum order.
+ * dbsr_objective_forward (the nn.Module's form): valid uint8 [B][1][H][W] or NULL, with L1 and L2 only (the
+ *   reference's other two metrics cannot take a mask): loss = sum(valid err) / (3 sum(valid) + 1e-12).
+ *   g      valid * (count * dloss/dpred) inside the crop, 0 outside: unnormalised (NULL: not written);
+ *          dloss/dpred = loss[2] * g / weight, the count being known only after the reduction (as dbsr_aligned_l1_*)
+ *   loss   {the metric, weight * the metric, weight / denominator};  stats as above with valid applied.
+ * dbsr_psnr_from_stats: per image 20 log10(max) - 10 log10(stats[b][0] / (stats[b][1] (+ 1e-12 when masked))),
+ *   max = max_values[b] (device, per image) or max_value when that is NULL; images whose value is inf or NaN are
+ *   dropped; out[0] = the mean of the rest, 0 if none is left; per_image [B] (NULL: not written) every value.
+ * dbsr_relu_grad_scaled: dbsr_relu_grad with gout multiplied by state's scale (an upstream gradient computed
+ *   outside the plan, entering a scaled backward). */
+enum { DBSR_METRIC_L1 = 0, DBSR_METRIC_L2 = 1, DBSR_METRIC_L2_SQRT = 2, DBSR_METRIC_CHARBONNIER = 3 };
+size_t dbsr_objective_workspace_bytes(int B, int H, int W);
+int dbsr_objective_step(int B, int H, int W, int boundary_ignore, int metric, float weight, const float* pred,
+                        const float* gt, const float* gextra, const void* state, dbsr_tensor dpre, float* loss,
+                        double* stats, void* workspace, size_t workspace_bytes, void* stream);
+int dbsr_objective_forward(int B, int H, int W, int boundary_ignore, int metric, float weight, const float* pred,
+                           const float* gt, const unsigned char* valid, float* g, float* loss, double* stats,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int dbsr_psnr_from_stats(int B, const double* stats, int masked, float max_value, const float* max_values, float* out,
+                         float* per_image, void* stream);
+int dbsr_relu_grad_scaled(int B, int C, int H, int W, const float* pred, const float* gout, const void* state,
+                          dbsr_tensor dpre, void* stream);
 /* wt[ci][co][ky][kx] = w[co][ci][kh-1-ky][kw-1-kx] (fp32): the dgrad conv's weights, to pack with
  * dbsr_conv_pack_weights(cout = cin, cin = cout). */
 int dbsr_dgrad_weights(const float* w, int cout, int cin, int kh, int kw, float* wt, void* stream);

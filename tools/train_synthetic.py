@@ -10,14 +10,17 @@ synthetic weights unless --weights names a state dict.
 --dtype picks the compute dtype (bf16 default; fp16 trains with DBSRTrainer's dynamic loss scaler, whose state is
 printed with the loss; fp32).
 
---lpips FILE adds a perceptual term, loss = L1 + W * LPIPS(pred, gt) with boundary_ignore 40 for both: FILE is
-anything evaluation.load_lpips_weights reads (the `lpips` package's LPIPS(net).state_dict() saved with torch.save;
-none are shipped).  The step then is the autograd loop -- net.train(); pred, _ = net(burst); loss.backward();
-torch.optim.Adam.step() -- instead of DBSRTrainer.step, whose fused objective has no LPIPS term: the metric's HIP
-backward (evaluation.LPIPS(differentiable=True)) hands dLPIPS/dpred to the network's HIP backward.
+The loss is DBSRTrainer's objective (dbsr_amd.objectives.Objective), so every choice below keeps the fused step --
+graph replay, the bucketed all-reduce, fused Adam, the device-side loss scaler:
+--metric l1|l2|l2_sqrt|charbonnier picks the pixel-wise term (PixelWiseError, boundary_ignore 40);
+--ssim W adds W * (1 - SSIM) with a dynamic range of 1, inside the plan;
+--lpips FILE adds --lpips-weight * LPIPS(pred, gt): FILE is anything evaluation.load_lpips_weights reads (the `lpips`
+package's LPIPS(net).state_dict() saved with torch.save; none are shipped).  The metric's HIP forward and backward
+(evaluation.LPIPS(differentiable=True)) run eagerly between the plan's forward and backward.
+The printed line is trainer.last_stats (Loss/total, Loss/rgb, Stat/psnr, ...), read back only where it is printed.
 
 Usage: python tools/train_synthetic.py IMAGE_DIR [--steps 100 --batch 16 --lr 1e-4 --seed 0 --dtype bf16 --save out.pth
-           --lpips FILE --lpips-weight 0.1 --lpips-net alex|vgg]"""
+           --metric l1 --ssim W --lpips FILE --lpips-weight 0.1 --lpips-net alex|vgg]"""
 import argparse
 import os
 import random
@@ -64,6 +67,8 @@ def main():
     ap.add_argument('--dtype', choices=['bf16', 'fp16', 'fp32'], default='bf16')
     ap.add_argument('--weights', default=None)
     ap.add_argument('--save', default=None)
+    ap.add_argument('--metric', choices=['l1', 'l2', 'l2_sqrt', 'charbonnier'], default='l1')
+    ap.add_argument('--ssim', type=float, default=None, help='weight of the (1 - SSIM) term')
     ap.add_argument('--lpips', default=None, help='LPIPS weights file: adds --lpips-weight * LPIPS(pred, gt) to the loss')
     ap.add_argument('--lpips-weight', type=float, default=0.1)
     ap.add_argument('--lpips-net', choices=['alex', 'vgg'], default='alex')
@@ -84,16 +89,16 @@ def main():
         net.load_state_dict(torch.load(args.weights, map_location='cpu'))
     dtype = {'bf16': torch.bfloat16, 'fp16': torch.float16, 'fp32': torch.float32}[args.dtype]
     net = net.to(dev).set_compute_dtype(dtype)
-    if args.lpips:
-        from dbsr_amd.evaluation import LPIPS
-        bi = 40
-        lpips = LPIPS(boundary_ignore=bi, type=args.lpips_net, weights=args.lpips, differentiable=True).to(dev)
-        net.train()
-        params = [p for p in net.parameters() if p.requires_grad]
-        opt = torch.optim.Adam(params, lr=args.lr)
-        scaler = torch.amp.GradScaler('cuda', enabled=dtype == torch.float16)
-    else:
-        trainer = DBSRTrainer(net, lr=args.lr)
+    objective = None                      # the built-in L1 plan
+    if args.metric != 'l1' or args.ssim is not None or args.lpips:
+        from dbsr_amd.objectives import Objective
+        extra = None
+        if args.lpips:
+            from dbsr_amd.evaluation import LPIPS
+            lpips = LPIPS(boundary_ignore=40, type=args.lpips_net, weights=args.lpips, differentiable=True).to(dev)
+            extra = lambda pred, gt: args.lpips_weight * lpips(pred, gt)          # noqa: E731
+        objective = Objective(args.metric, ssim=args.ssim, extra=extra, boundary_ignore=40)
+    trainer = DBSRTrainer(net, lr=args.lr, objective=objective)
     btp = {'max_translation': args.max_translation, 'max_rotation': args.max_rotation, 'max_shear': 0.0,
            'max_scale': 0.0, 'border_crop': args.border_crop}
     proc = SyntheticBurstProcessing(args.crop, args.burst, args.factor, burst_transformation_params=btp,
@@ -102,25 +107,13 @@ def main():
                                     device=dev, generator=torch.Generator(device=dev).manual_seed(args.seed))
     for step in range(args.steps):
         d = proc([load_rgb8(random.choice(files)) for _ in range(args.batch)])
-        if args.lpips:
-            gt = d['frame_gt']
-            pred, _ = net(d['burst'])
-            l1 = torch.nn.functional.l1_loss(pred[..., bi:-bi, bi:-bi].float(), gt[..., bi:-bi, bi:-bi].float())
-            lp = lpips(pred, gt)
-            loss = l1 + args.lpips_weight * lp
-            opt.zero_grad(set_to_none=True)
-            scaler.scale(loss).backward()
-            scaler.step(opt)
-            scaler.update()
-            if step % 10 == 0 or step == args.steps - 1:
-                print('step %d  loss %.5f  l1 %.5f  lpips %.5f'
-                      % (step, float(loss.detach()), float(l1.detach()), float(lp.detach())), flush=True)
-            continue
         loss = trainer.step(d['burst'], d['frame_gt'])
         if step % 10 == 0 or step == args.steps - 1:
             ls = trainer.loss_scale_state()          # (a small device-to-host copy: only where the loss is printed)
             scaler = '' if ls is None else '  scale %g  applied %d  skipped %d' % (ls['scale'], ls['steps'], ls['skipped'])
-            print('step %d  loss %.5f%s' % (step, float(loss), scaler), flush=True)
+            stats = trainer.last_stats or {}
+            terms = ''.join('  %s %.5f' % (k, float(v)) for k, v in stats.items() if k != 'Loss/total')
+            print('step %d  loss %.5f%s%s' % (step, float(loss), terms, scaler), flush=True)
     if args.save:
         torch.save(net.state_dict(), args.save)
 
