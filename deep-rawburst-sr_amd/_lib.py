@@ -15,6 +15,9 @@ LIB_PATH = os.environ.get('DBSR_HIP_LIB', os.path.join(_HERE, 'libdbsr_hip.so'))
 DBSR_F32, DBSR_BF16, DBSR_F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
 OUT_NHWC, OUT_SHUFFLE, OUT_NCHW_F32 = 0, 1, 2
+# what dbsr_conv_kernel_for returns (dbsr_hip.h DBSR_CONV_*)
+(CONV_GENERIC, CONV_TILED, CONV_PIPE, CONV_SHUFFLE, CONV_WS, CONV_POINTWISE, CONV_NARROW, CONV_KS128,
+ CONV_SMALL) = range(9)
 ABI_VERSION = 23
 SRC_F32_NCHW, SRC_U8_NHWC = 0, 1
 POST_GAINS, POST_CCM, POST_GAMMA, POST_SMOOTHSTEP = 1, 2, 4, 8

@@ -1246,6 +1246,17 @@ int num_cus() {
     return g_num_cus;
 }
 
+// The compile-time epilogue of the pipelined, weight-stationary and 128-channel kernels: 5 gated (the training
+// dgrad), 1 bias + ReLU, 2 bias + residual + post-ReLU, 3 bias only -- the forward's three conv flavours -- and the
+// run-time epilogue 0 otherwise
+int epi_code(const ConvK& k) {
+    if (k.gt) return 5;
+    if (!k.r && k.act == DBSR_ACT_RELU) return 1;
+    if (k.r && k.act == DBSR_ACT_NONE && k.post_act == DBSR_ACT_RELU) return 2;
+    if (!k.r && k.act == DBSR_ACT_NONE) return 3;
+    return 0;
+}
+
 template <typename T, int WM, int TW, int TH>
 int launch_pipe(const ConvK& k, int n_frames, hipStream_t s) {
     const int tiles_x = (k.out_w + TW - 1) / TW, tiles_y = (k.out_h + TH - 1) / TH;
@@ -1258,13 +1269,9 @@ int launch_pipe(const ConvK& k, int n_frames, hipStream_t s) {
     const int cap = k.max_blocks > 0 ? std::min(k.max_blocks, num_cus()) : num_cus();
     int grid = (int)std::min<long long>(nt, cap);
     grid = (grid + 7) / 8 * 8;
-    // compile-time epilogues for the forward's three conv flavours, run-time otherwise
-    int epi = 0;                        // (a gated conv, the training dgrad, takes the run-time epilogue 0, or 5
-    if (k.gt) epi = (TW == 32 && TH == 16) ? 5 : 0;   // at the 32x16 tile where 0's prefetched gate spills)
+    int epi = epi_code(k);              // (a gated conv, the training dgrad, takes the run-time epilogue 0, or 5
+    if (epi == 5) epi = (TW == 32 && TH == 16) ? 5 : 0;   // at the 32x16 tile where 0's prefetched gate spills)
     else if (k.head_cout > 0) epi = 4;
-    else if (!k.r && k.act == DBSR_ACT_RELU) epi = 1;
-    else if (k.r && k.act == DBSR_ACT_NONE && k.post_act == DBSR_ACT_RELU) epi = 2;
-    else if (!k.r && k.act == DBSR_ACT_NONE) epi = 3;
     // 6: bias + LeakyReLU, PWC-Net's convs: run-time epilogue 0 spilled 48 VGPRs at the 32x16 tile, 6 none
     // (pwc.refiner0 46 -> 38 us on the chip, profiles/r06e6_pipe_epi6_ab.txt)
     else if (!k.r && k.act == DBSR_ACT_LRELU) epi = 6;
@@ -1289,15 +1296,23 @@ int launch_pipe(const ConvK& k, int n_frames, hipStream_t s) {
     return 0;
 }
 
+// what the pipelined, weight-stationary and 128-channel kernels ask alike: a 16-bit 3x3/s1/p1/d1 conv with an NHWC
+// output of the input dtype ...
+bool conv3x3_16(const dbsr_conv_desc* d) {
+    return is16(d->x.dtype) && !d->precise && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 &&
+           d->dil == 1 && d->out_mode == DBSR_OUT_NHWC && d->y.dtype == d->x.dtype;
+}
+// ... whose y / residual / gate slices start and step on 8 channels (16-B runs), the gate of the output dtype
+bool slices_aligned8(const dbsr_conv_desc* d) {
+    if (d->y.ld % 8 || d->y.c0 % 8 || (d->res.ptr && (d->res.ld % 8 || d->res.c0 % 8))) return false;
+    return !(d->gate.ptr && (d->gate.ld % 8 || d->gate.c0 % 8 || d->gate.dtype != d->y.dtype));
+}
+
 // which pipelined tile serves `d` (0: none): bf16 3x3/s1/p1/d1 with Cin % 32 == 0 after padding, an
 // aligned NHWC bf16 output (staged epilogue), and enough tiles to fill the chip
 int g_pipe_enabled = 1;
 int pick_pipe(const dbsr_conv_desc* d) {
-    if (!g_pipe_enabled || !is16(d->x.dtype) || d->precise || d->kh != 3 || d->kw != 3 || d->stride != 1 ||
-        d->pad != 1 || d->dil != 1 || d->cin <= 16 || d->out_mode != DBSR_OUT_NHWC || d->y.dtype != d->x.dtype)
-        return 0;
-    if (d->y.ld % 8 || d->y.c0 % 8 || d->cout % 8 || (d->res.ptr && (d->res.ld % 8 || d->res.c0 % 8))) return 0;
-    if (d->gate.ptr && (d->gate.ld % 8 || d->gate.c0 % 8 || d->gate.dtype != d->y.dtype)) return 0;
+    if (!g_pipe_enabled || !conv3x3_16(d) || !slices_aligned8(d) || d->cin <= 16 || d->cout % 8) return 0;
     if (cin_pad(d->cin) * 2 + 64 > ZERO_PAGE_BYTES || d->cout > 512) return 0;
     if ((long long)d->in_h * d->in_w * d->x.ld * 2 >= (1LL << 31)) return 0;   // 32-bit buffer offsets per frame
     int cfg = 0, tw = 0, th = 8, wm = 0;
@@ -1920,16 +1935,11 @@ inline bool ws_short(const dbsr_conv_desc* d) {
     return !ws_narrow(d) && d->cin > 32 && d->out_w % 16 == 0 && d->out_h % 16 == 0 &&
            (long long)d->n_frames * (d->out_w / 16) * (d->out_h / 16) * ((d->cout + 63) / 64) < 128;
 }
-// (d: the selection view; g: the launch geometry when it differs -- a plan_h slab -- which must suit the tile
-// chosen for d; the block count then follows g's own tile count)
-int pick_ws(const dbsr_conv_desc* d, const dbsr_conv_desc* g = nullptr) {
-    if (!g_ws_enabled || !is16(d->x.dtype) || d->precise || d->kh != 3 || d->kw != 3 || d->stride != 1 ||
-        d->pad != 1 || d->dil != 1 || d->cin <= 16 || d->cin > 64 || d->out_mode != DBSR_OUT_NHWC ||
-        d->y.dtype != d->x.dtype)
-        return 0;
-    if (d->gate.ptr && (d->gate.ld % 8 || d->gate.c0 % 8 || d->gate.dtype != d->y.dtype)) return 0;
-    if (d->y.ld % 8 || d->y.c0 % 8 || d->cout % 8 || d->cout > 512 ||
-        (d->res.ptr && (d->res.ld % 8 || d->res.c0 % 8)))
+// (d: the selection view; g: the launch geometry -- d, or a plan_h slab, which must suit the tile chosen for d
+// (-1 if not); the block count follows g's own tile count)
+int pick_ws(const dbsr_conv_desc* d, const dbsr_conv_desc* g) {
+    if (!g_ws_enabled || !conv3x3_16(d) || !slices_aligned8(d) || d->cin <= 16 || d->cin > 64 || d->cout % 8 ||
+        d->cout > 512)
         return 0;
     const bool narrow = ws_narrow(d);
     const int tw = narrow ? 64 : 16, th = (narrow || ws_short(d)) ? 8 : 16, wm = narrow ? 32 : 64;
@@ -1942,8 +1952,7 @@ int pick_ws(const dbsr_conv_desc* d, const dbsr_conv_desc* g = nullptr) {
     const long long nsp = (long long)d->n_frames * (d->out_w / tw) * (d->out_h / th);
     const int cus = d->max_blocks > 0 ? std::min(d->max_blocks, num_cus()) : num_cus();
     if (cus / 8 / nct < 1 || nsp * nct < 64) return 0;
-    if (!g) g = d;
-    if (g->out_h % th) return -1;                                             // slab rows do not tile
+    if (g->out_h % th) return -1;                                           // slab rows do not tile
     const long long nsp_g = (long long)g->n_frames * (g->out_w / tw) * (g->out_h / th);
     const long long want = (nsp_g + 7) / 8;                                   // spatial streams per XCD
     const long long spx = std::max<long long>(1, std::min<long long>(cus / 8 / nct, want));
@@ -1955,15 +1964,10 @@ int launch_ws(const ConvK& k, const dbsr_conv_desc* d, int px, hipStream_t s) {
     const int tiles_x = k.out_w / TW, tiles_y = k.out_h / TH;
     const int nct = (k.cout + WM - 1) / WM;
     const int nsp = d->n_frames * tiles_x * tiles_y;
-    int epi = 0;                        // (a gated conv, the training dgrad, takes epilogue 5)
-    if (k.gt) epi = 5;
-    else if (!k.r && k.act == DBSR_ACT_RELU) epi = 1;
-    else if (k.r && k.act == DBSR_ACT_NONE && k.post_act == DBSR_ACT_RELU) epi = 2;
-    else if (!k.r && k.act == DBSR_ACT_NONE) epi = 3;
-#define DBSR_WS_LAUNCH(E)                                                                                         \
+#define DBSR_WS_LAUNCH(E)                                                                                       \
     hipLaunchKernelGGL((conv3x3_ws_kernel<T, WM, TW, TH, NCH, E>), dim3(8 * px), dim3(512), 0, s, k, tiles_x,    \
                        tiles_y, nct, nsp, px)
-    switch (epi) {
+    switch (epi_code(k)) {
         case 1: DBSR_WS_LAUNCH(1); break;
         case 2: DBSR_WS_LAUNCH(2); break;
         case 3: DBSR_WS_LAUNCH(3); break;
@@ -1981,23 +1985,14 @@ int g_ks128_enabled = 1;
 // and at least 128 tiles (the weight predictor's input conv and ResBlocks, merging.py:86-90, 98-101, and their
 // gated dgrads in the training step)
 bool use_ks128(const dbsr_conv_desc* d) {
-    if (!g_ks128_enabled || !is16(d->x.dtype) || d->precise || d->kh != 3 || d->kw != 3 || d->stride != 1 ||
-        d->pad != 1 || d->dil != 1 || cin_pad(d->cin) != 128 || d->cout != 128 || d->out_mode != DBSR_OUT_NHWC ||
-        d->y.dtype != d->x.dtype)
+    if (!g_ks128_enabled || !conv3x3_16(d) || !slices_aligned8(d) || cin_pad(d->cin) != 128 || d->cout != 128)
         return false;
-    if (d->y.ld % 8 || d->y.c0 % 8 || (d->res.ptr && (d->res.ld % 8 || d->res.c0 % 8))) return false;
-    if (d->gate.ptr && (d->gate.ld % 8 || d->gate.c0 % 8 || d->gate.dtype != d->y.dtype)) return false;
     if (d->out_w % ks128::TW || d->out_h % ks128::TH || (d->plan_h > 0 && d->plan_h != d->out_h)) return false;
     if ((long long)d->in_h * d->in_w * d->x.ld * 2 >= (1LL << 31)) return false;   // 32-bit buffer offsets per frame
     return (long long)d->n_frames * (d->out_w / ks128::TW) * (d->out_h / ks128::TH) >= 128;
 }
 int launch_ks128(const ConvK& k, const dbsr_conv_desc* d, hipStream_t s) {
-    int epi = 0;                        // the pipelined kernel's compile-time epilogues 1-3, run-time 0 otherwise,
-    if (k.gt) epi = 5;                  // 5 with the gate
-    else if (!k.r && k.act == DBSR_ACT_RELU) epi = 1;
-    else if (k.r && k.act == DBSR_ACT_NONE && k.post_act == DBSR_ACT_RELU) epi = 2;
-    else if (!k.r && k.act == DBSR_ACT_NONE) epi = 3;
-    return ks128_launch(k, d->n_frames, d->x.dtype == DBSR_F16, epi, k.max_blocks, num_cus(), s);
+    return ks128_launch(k, d->n_frames, d->x.dtype == DBSR_F16, epi_code(k), k.max_blocks, num_cus(), s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2313,7 +2308,7 @@ bool resblock_out_disjoint(const dbsr_conv_desc* c1, const dbsr_conv_desc* c2, c
 
 // the fused ResBlock applies: c1 = conv1 (x -> any, ReLU), c2 = conv2 (-> y, residual x, post-ReLU), both
 // 16-bit 3x3/s1/p1/d1 C -> C with chunk-major weight copies, NHWC slices aligned; returns C (32: resblock32_kernel,
-// frames a multiple of 32 x 16; 64: resblock64_kernel, frames a multiple of 16 x 16) or 0
+// frames a multiple of 32 x 16; 64: resblock64_kernel, frames a multiple of 16 x 8, rb64::TW x TH) or 0
 int resblock_channels(const dbsr_conv_desc* c1, const dbsr_conv_desc* c2) {
     if (!c1 || !c2) return 0;
     const int C = c1->cin;
@@ -2347,22 +2342,6 @@ int resblock_channels(const dbsr_conv_desc* c1, const dbsr_conv_desc* c2) {
     return (long long)c1->in_h * c1->in_w * c1->x.ld * 2 < (1LL << 31) ? C : 0;
 }
 
-template <typename T>
-int dispatch_ws(int px, const ConvK& k, const dbsr_conv_desc* d, const dbsr_conv_desc* sel, hipStream_t s) {
-    if (ws_narrow(sel)) return launch_ws<T, 32, 64, 8, 1>(k, d, px, s);
-    if (ws_short(sel)) return launch_ws<T, 64, 16, 8, 2>(k, d, px, s);
-    if (k.CG / 4 == 1) return launch_ws<T, 64, 16, 16, 1>(k, d, px, s);
-    return launch_ws<T, 64, 16, 16, 2>(k, d, px, s);
-}
-
-template <typename T>
-int dispatch_pipe(int cfg, const ConvK& k, const dbsr_conv_desc* d, hipStream_t s) {
-    if (cfg == 1) return launch_pipe<T, 64, 48, 8>(k, d->n_frames, s);
-    if (cfg == 3) return launch_pipe<T, 64, 16, 16>(k, d->n_frames, s);
-    if (cfg == 4) return launch_pipe<T, 64, 32, 16>(k, d->n_frames, s);
-    return launch_pipe<T, 32, 64, 8>(k, d->n_frames, s);
-}
-
 template <typename T, int MT, int NT, typename XT = T>
 int launch_conv(const ConvK& k0, hipStream_t s) {
     ConvK k = k0;
@@ -2393,8 +2372,10 @@ int choose_ksplit(const ConvK& k, int mt, int nt) {
     sp = std::min(sp, 32);
     return std::max(sp, 1);
 }
-size_t splitk_bytes(const ConvK& k, int sp) {
-    return sp > 1 ? (size_t)sp * k.npix * k.cw * sizeof(float) : 0;
+// fp32 partials of `sp` K slices of the launch geometry `d` (ConvK's npix x cw each)
+size_t splitk_bytes(const dbsr_conv_desc* d, int sp) {
+    const int npix = (int)((long long)d->n_frames * d->out_h * d->out_w);
+    return sp > 1 ? (size_t)sp * npix * round_up(d->cout, 4) * sizeof(float) : 0;
 }
 // generic kernel: the largest tile that still gives >= 2 blocks per CU (512 blocks); tiny PWC levels
 // (a few hundred pixels) fall through to 16 x 64-pixel tiles (and split-K) for parallelism
@@ -2569,69 +2550,6 @@ int tiled_ksplit(const dbsr_conv_desc* d, int& wm, int& wn) {
     wm = wm0;
     wn = 64;
     return sp;
-}
-
-template <typename T, int D>
-int dispatch_tiled_d(const ConvK& k0, const dbsr_conv_desc* d, const dbsr_conv_desc* sel, hipStream_t s) {
-    int wm, wn;
-    pick_tiled_tile(sel, wm, wn);
-    ConvK k = k0;
-    k.ksplit = tiled_ksplit(sel, wm, wn);
-    if (k.ksplit > 1 && splitk_bytes(k, k.ksplit) > d->workspace_bytes) {
-        k.ksplit = 1;
-        pick_tiled_tile(sel, wm, wn);
-    }
-    if (wm == 64) return launch_tiled<T, 64, 64, D>(k, d->n_frames, s);
-    if (wn == 128) return launch_tiled<T, 32, 128, D>(k, d->n_frames, s);
-    if (wn == 64) return launch_tiled<T, 32, 64, D>(k, d->n_frames, s);
-    return launch_tiled<T, 32, 16, D>(k, d->n_frames, s);
-}
-
-ConvK make_convk(const dbsr_conv_desc* d);
-
-int slab_misfit(const dbsr_conv_desc* d, const dbsr_conv_desc* sel) {
-    dbsr_set_error("conv2d: a %d-row slab cannot take the tile chosen for plan_h = %d rows (use a multiple of 16)",
-                   d->out_h, sel->out_h);
-    return DBSR_E_ARG;
-}
-
-// d: the launch geometry; sel: the selection view (sel_view)
-template <typename T>
-int dispatch_conv(const ConvK& k, const dbsr_conv_desc* d, const dbsr_conv_desc* sel, hipStream_t s) {
-    if constexpr (sizeof(T) == 2) {
-        const int px = pick_ws(sel, d);
-        if (px < 0) return slab_misfit(d, sel);
-        if (px) return dispatch_ws<T>(px, k, d, sel, s);
-        if (use_ks128(sel)) return launch_ks128(k, d, s);
-        const int cfg = pick_pipe(sel);
-        if (cfg && !pipe_fits(cfg, d)) return slab_misfit(d, sel);
-        if (cfg) return dispatch_pipe<T>(cfg, k, d, s);
-        if (use_narrow(sel)) return launch_narrow<T>(k, d, s);
-        if (use_small(sel)) return launch_small<T>(k, d, s);
-    }
-    if (use_tiled(sel)) {
-        switch (d->dil) {
-            case 1: return dispatch_tiled_d<T, 1>(k, d, sel, s);
-            case 2: return dispatch_tiled_d<T, 2>(k, d, sel, s);
-            case 4: return dispatch_tiled_d<T, 4>(k, d, sel, s);
-            default:
-                if constexpr (sizeof(T) == 2) return dispatch_tiled_d<T, 8>(k, d, sel, s);
-                dbsr_set_error("conv2d: no fp32 tile for dilation %d", d->dil);
-                return DBSR_E_ARG;
-        }
-    }
-    int best_m, best_n;
-    const ConvK ksel = sel == d ? k : make_convk(sel);
-    pick_generic_tile(ksel, best_m, best_n);
-    ConvK kk = k;
-    kk.ksplit = choose_ksplit(ksel, best_m, best_n);
-    if (kk.ksplit > 1 && splitk_bytes(k, kk.ksplit) > d->workspace_bytes) kk.ksplit = 1;
-#define DBSR_CONV_CASE(M, N) if (best_m == M && best_n == N) return launch_conv<T, M, N>(kk, s);
-    DBSR_CONV_CASE(4, 4) DBSR_CONV_CASE(4, 2) DBSR_CONV_CASE(4, 1)
-    DBSR_CONV_CASE(2, 4) DBSR_CONV_CASE(2, 2) DBSR_CONV_CASE(2, 1)
-    DBSR_CONV_CASE(1, 4) DBSR_CONV_CASE(1, 2) DBSR_CONV_CASE(1, 1)
-#undef DBSR_CONV_CASE
-    return launch_conv<T, 1, 1>(kk, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3196,6 +3114,154 @@ ConvK make_convk(const dbsr_conv_desc* d) {
     return k;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The dispatch decision for one descriptor.  conv_plan holds the only copy of the order the kernels are tried in:
+// dbsr_conv2d launches what it returns (launch_plan) and every host query (kernel_for, dispatch_variant,
+// workspace_bytes, lane_reach) reads it, so a new kernel is wired in here and in launch_plan, nowhere else.
+// ------------------------------------------------------------------------------------------------
+struct ConvPlan {
+    int kernel;             // DBSR_CONV_*
+    bool misfit;            // a plan_h slab cannot take the tile chosen for the whole image: dbsr_conv2d refuses it
+    bool precise16;         // generic kernel on fp32 MFMA over 16-bit activations (precise): 1 x nt tile, never split
+    int wm;                 // couts per tile: weight-stationary, pipelined, LDS-tiled
+    int tw, th, nch, px;    // weight-stationary: pixel tile, conv3x3_ws_kernel's NCH, blocks per XCD (pick_ws)
+    int pipe_cfg;           // pipelined: pick_pipe's tile 1-4
+    int wn;                 // LDS-tiled: pixels per tile
+    int mt, nt;             // generic: 16-cout x 64-pixel units per tile
+    int ksplit;             // K slices, LDS-tiled or generic (1: none)
+    size_t workspace;       // bytes of fp32 partials those slices need (0: none)
+};
+
+// The pipelined step of the chain.  On its own it answers dbsr_conv_head_ok: dbsr_conv2d_head launches the pipelined
+// kernel itself, whatever ranks before it in conv_plan.
+bool plan_pipe(ConvPlan& p, const dbsr_conv_desc* sel, const dbsr_conv_desc* d) {
+    p.pipe_cfg = pick_pipe(sel);
+    if (!p.pipe_cfg) return false;
+    p.kernel = DBSR_CONV_PIPE;
+    p.wm = p.pipe_cfg == 2 ? 32 : 64;
+    p.misfit = !pipe_fits(p.pipe_cfg, d);
+    return true;
+}
+
+// d: the launch geometry, every choice taken on its selection view (sel_view); workspace_avail: the split-K scratch
+// the launch may use (SIZE_MAX: what the conv would take).  Allocates nothing.
+ConvPlan conv_plan(const dbsr_conv_desc* d, size_t workspace_avail) {
+    dbsr_conv_desc v;
+    const dbsr_conv_desc* sel = sel_view(d, v);
+    const bool x16 = is16(d->x.dtype);
+    ConvPlan p = {};
+    p.ksplit = 1;
+    if (d->precise && x16) {
+        // 16-bit activations, fp32-packed weights, fp32 MFMA: small fp32-output heads (the RGB predictor)
+        const long long npix = (long long)sel->n_frames * sel->out_h * sel->out_w;
+        p.kernel = DBSR_CONV_GENERIC;
+        p.precise16 = true;
+        p.mt = 1;
+        p.nt = npix >= 512 * 256 ? 4 : npix >= 512 * 128 ? 2 : 1;
+        return p;
+    }
+    // (a ConvK of the selection view only where a choice reads one: here and for the generic kernel)
+    if (sel->out_mode == DBSR_OUT_SHUFFLE && use_upsample(sel, make_convk(sel))) {
+        p.kernel = DBSR_CONV_SHUFFLE;
+        return p;
+    }
+    if (use_pointwise(sel)) { p.kernel = DBSR_CONV_POINTWISE; return p; }
+    if (x16) {
+        p.px = pick_ws(sel, d);
+        if (p.px) {
+            const bool narrow = ws_narrow(sel), low = narrow || ws_short(sel);
+            p.kernel = DBSR_CONV_WS;
+            p.misfit = p.px < 0;
+            p.wm = narrow ? 32 : 64;
+            p.tw = narrow ? 64 : 16;
+            p.th = low ? 8 : 16;
+            p.nch = narrow ? 1 : low ? 2 : cin_pad(sel->cin) / 32;      // (16 < cin <= 64)
+            return p;
+        }
+        if (use_ks128(sel)) { p.kernel = DBSR_CONV_KS128; return p; }
+        if (plan_pipe(p, sel, d)) return p;
+        if (use_narrow(sel)) { p.kernel = DBSR_CONV_NARROW; return p; }
+        if (use_small(sel)) { p.kernel = DBSR_CONV_SMALL; return p; }
+    }
+    if (use_tiled(sel)) {               // (use_tiled admits dilation 8 for 16-bit inputs only: no fp32 tile fits the LDS)
+        p.kernel = DBSR_CONV_TILED;
+        pick_tiled_tile(sel, p.wm, p.wn);
+        p.ksplit = tiled_ksplit(sel, p.wm, p.wn);
+        p.workspace = splitk_bytes(d, p.ksplit);
+        if (p.workspace > workspace_avail) {            // no room for the partials: unsplit, on an unsplit conv's tile
+            p.ksplit = 1;
+            p.workspace = 0;
+            pick_tiled_tile(sel, p.wm, p.wn);
+        }
+        return p;
+    }
+    p.kernel = DBSR_CONV_GENERIC;
+    const ConvK ksel = make_convk(sel);
+    pick_generic_tile(ksel, p.mt, p.nt);
+    p.ksplit = choose_ksplit(ksel, p.mt, p.nt);
+    p.workspace = splitk_bytes(d, p.ksplit);
+    if (p.workspace > workspace_avail) {                // no room for the partials: unsplit, the tile kept
+        p.ksplit = 1;
+        p.workspace = 0;
+    }
+    return p;
+}
+
+template <typename T, int D>
+int launch_tiled_tile(const ConvPlan& p, const ConvK& k, int n_frames, hipStream_t s) {
+    if (p.wm == 64) return launch_tiled<T, 64, 64, D>(k, n_frames, s);
+    if (p.wn == 128) return launch_tiled<T, 32, 128, D>(k, n_frames, s);
+    if (p.wn == 64) return launch_tiled<T, 32, 64, D>(k, n_frames, s);
+    return launch_tiled<T, 32, 16, D>(k, n_frames, s);
+}
+
+// Launches the plan.  T: the activations' type; k, d: the launch geometry, k.ksplit the plan's.
+template <typename T>
+int launch_plan(const ConvPlan& p, const ConvK& k, const dbsr_conv_desc* d, hipStream_t s) {
+    if constexpr (sizeof(T) == 2) {
+        if (p.precise16) {
+            if (p.nt == 4) return launch_conv<float, 1, 4, T>(k, s);
+            if (p.nt == 2) return launch_conv<float, 1, 2, T>(k, s);
+            return launch_conv<float, 1, 1, T>(k, s);
+        }
+        switch (p.kernel) {
+            case DBSR_CONV_SHUFFLE: return launch_upsample<T>(k, s);
+            case DBSR_CONV_POINTWISE: return launch_pointwise<T>(k, s);
+            case DBSR_CONV_WS:
+                if (p.wm == 32) return launch_ws<T, 32, 64, 8, 1>(k, d, p.px, s);
+                if (p.th == 8) return launch_ws<T, 64, 16, 8, 2>(k, d, p.px, s);
+                if (p.nch == 1) return launch_ws<T, 64, 16, 16, 1>(k, d, p.px, s);
+                return launch_ws<T, 64, 16, 16, 2>(k, d, p.px, s);
+            case DBSR_CONV_KS128: return launch_ks128(k, d, s);
+            case DBSR_CONV_PIPE:
+                if (p.pipe_cfg == 1) return launch_pipe<T, 64, 48, 8>(k, d->n_frames, s);
+                if (p.pipe_cfg == 3) return launch_pipe<T, 64, 16, 16>(k, d->n_frames, s);
+                if (p.pipe_cfg == 4) return launch_pipe<T, 64, 32, 16>(k, d->n_frames, s);
+                return launch_pipe<T, 32, 64, 8>(k, d->n_frames, s);
+            case DBSR_CONV_NARROW: return launch_narrow<T>(k, d, s);
+            case DBSR_CONV_SMALL: return launch_small<T>(k, d, s);
+            default: break;
+        }
+    }
+    if (p.kernel == DBSR_CONV_TILED) {
+        switch (d->dil) {
+            case 1: return launch_tiled_tile<T, 1>(p, k, d->n_frames, s);
+            case 2: return launch_tiled_tile<T, 2>(p, k, d->n_frames, s);
+            case 4: return launch_tiled_tile<T, 4>(p, k, d->n_frames, s);
+            default:
+                if constexpr (sizeof(T) == 2) return launch_tiled_tile<T, 8>(p, k, d->n_frames, s);
+                dbsr_set_error("conv2d: no fp32 tile for dilation %d", d->dil);
+                return DBSR_E_ARG;
+        }
+    }
+#define DBSR_CONV_CASE(M, N) if (p.mt == M && p.nt == N) return launch_conv<T, M, N>(k, s);
+    DBSR_CONV_CASE(4, 4) DBSR_CONV_CASE(4, 2) DBSR_CONV_CASE(4, 1)
+    DBSR_CONV_CASE(2, 4) DBSR_CONV_CASE(2, 2) DBSR_CONV_CASE(2, 1)
+    DBSR_CONV_CASE(1, 4) DBSR_CONV_CASE(1, 2) DBSR_CONV_CASE(1, 1)
+#undef DBSR_CONV_CASE
+    return launch_conv<T, 1, 1>(k, s);
+}
+
 }  // namespace
 
 #ifdef DBSR_PIPE_STAMPS
@@ -3210,112 +3276,62 @@ extern "C" int dbsr_diag_pipe_stamps(unsigned long long* host, long long n) {
 }
 #endif
 
-// the order dbsr_conv2d tries the kernels in, on the selection view (16-bit kernels first)
-int kernel_for(const dbsr_conv_desc* d) {
-    dbsr_conv_desc v;
-    const dbsr_conv_desc* sel = sel_view(d, v);
-    if (d->precise) return 0;
-    if (use_upsample(sel, make_convk(sel))) return 3;
-    if (use_pointwise(sel)) return 5;
-    if (is16(d->x.dtype)) {
-        if (pick_ws(sel)) return 4;
-        if (use_ks128(sel)) return 7;
-        if (pick_pipe(sel)) return 2;
-        if (use_narrow(sel)) return 6;
-        if (use_small(sel)) return 8;
-    }
-    return use_tiled(sel) ? 1 : 0;
-}
-
 // Host model of the highest channel of a pixel (c0 included) that any lane of the kernel dbsr_conv2d launches
 // for `d` touches in y (which 0), the residual (1) or the gate (2); -1 when that tensor is unused (or y is not
 // NHWC).  The pipelined and weight-stationary kernels address a partial cout tile's lanes through
 // pipe_lane_ch / ws_lane_ch, enumerated here over the last cout tile; the other kernels bound every element by
 // cout (epilogue_px's nvalid) and store only runs below cout; the weight-stationary residual arrives through a
 // buffer resource that spans its frame's ld-wide pixels, so a run past the last pixel lands zeros.
-int conv_lane_reach(const dbsr_conv_desc* d, int which) {
+int conv_lane_reach(const dbsr_conv_desc* d, const ConvPlan& p, int which) {
     const dbsr_tensor& t = which == 0 ? d->y : which == 1 ? d->res : d->gate;
     if (!t.ptr || d->out_mode != DBSR_OUT_NHWC) return -1;
-    dbsr_conv_desc v;
-    const dbsr_conv_desc* sel = sel_view(d, v);
-    const int kf = kernel_for(d);
     int hi = d->cout - 1;
-    if (kf == 2 && which > 0) {
-        const int wm = pick_pipe(sel) == 2 ? 32 : 64;
-        const int cb = (d->cout - 1) / wm * wm;                 // the last, possibly partial, cout tile
-        for (int h = 0; h < wm / 32; ++h)
+    if (p.kernel == DBSR_CONV_PIPE && which > 0) {
+        const int cb = (d->cout - 1) / p.wm * p.wm;             // the last, possibly partial, cout tile
+        for (int h = 0; h < p.wm / 32; ++h)
             for (int g = 0; g < 4; ++g) hi = std::max(hi, pipe_lane_ch(cb, h, g, d->cout) + 7);
-    } else if (kf == 4 && which == 2) {
-        const int wm = ws_narrow(sel) ? 32 : 64;
-        const int ctb = (d->cout - 1) / wm * wm;
-        for (int wc = 0; wc < wm / 32; ++wc)
+    } else if (p.kernel == DBSR_CONV_WS && which == 2) {
+        const int ctb = (d->cout - 1) / p.wm * p.wm;
+        for (int wc = 0; wc < p.wm / 32; ++wc)
             for (int g = 0; g < 4; ++g) hi = std::max(hi, ws_lane_ch(ctb, wc, g, d->cout) + 7);
-    } else if (kf == 4 && which == 1) {
+    } else if (p.kernel == DBSR_CONV_WS && which == 1) {
         return std::min(t.c0 + ((d->cout - 1) / 64 + 1) * 64 - 1, t.ld - 1);   // clamped by the frame's resource
     }
     return t.c0 + hi;
 }
 
+// The queries plan as the launch would with all the workspace the conv could ask for.
 extern "C" int dbsr_conv_lane_reach(const dbsr_conv_desc* d, int which) {
-    return (d && which >= 0 && which <= 2) ? conv_lane_reach(d, which) : -2;
+    return (d && which >= 0 && which <= 2) ? conv_lane_reach(d, conv_plan(d, SIZE_MAX), which) : -2;
 }
 
 extern "C" int dbsr_conv_kernel_for(const dbsr_conv_desc* d) {
-    return d ? kernel_for(d) : -1;
+    return d ? conv_plan(d, SIZE_MAX).kernel : -1;
 }
 
 extern "C" int dbsr_conv_dispatch_variant(const dbsr_conv_desc* d) {
     if (!d) return -1;
-    dbsr_conv_desc v;
-    const dbsr_conv_desc* sel = sel_view(d, v);
-    const int kf = kernel_for(d);
+    const ConvPlan p = conv_plan(d, SIZE_MAX);
     int var = 0;
-    if (d->precise) {
-        const long long np = (long long)sel->n_frames * sel->out_h * sel->out_w;
-        var = np >= 512 * 256 ? 4 : np >= 512 * 128 ? 2 : 1;
-    } else if (kf == 4) {
-        var = ws_narrow(sel) ? 6408 : ws_short(sel) ? 1608 : 1616;
-    } else if (kf == 7) {
-        var = ks128::TW * 100 + ks128::TH;
-    } else if (kf == 2) {
-        var = pick_pipe(sel);
-    } else if (kf == 1) {
-        int wm, wn;
-        pick_tiled_tile(sel, wm, wn);
-        const int sp = tiled_ksplit(sel, wm, wn);
-        var = (sp > 1 ? sp * 100000 : 0) + wm * 1000 + wn;
-    } else if (kf == 0) {
-        const ConvK k = make_convk(sel);
-        int m, n;
-        pick_generic_tile(k, m, n);
-        var = m * 10000 + n * 1000 + choose_ksplit(k, m, n);
-    }
-    return kf * 1000000 + var;
+    if (p.precise16) var = p.nt;
+    else if (p.kernel == DBSR_CONV_WS) var = p.tw * 100 + p.th;
+    else if (p.kernel == DBSR_CONV_KS128) var = ks128::TW * 100 + ks128::TH;
+    else if (p.kernel == DBSR_CONV_PIPE) var = p.pipe_cfg;
+    else if (p.kernel == DBSR_CONV_TILED) var = (p.ksplit > 1 ? p.ksplit * 100000 : 0) + p.wm * 1000 + p.wn;
+    else if (p.kernel == DBSR_CONV_GENERIC) var = p.mt * 10000 + p.nt * 1000 + p.ksplit;
+    return p.kernel * 1000000 + var;
 }
 
 extern "C" int dbsr_conv_head_ok(const dbsr_conv_desc* d) {
     if (!d) return 0;
     dbsr_conv_desc v;
-    const dbsr_conv_desc* sel = sel_view(d, v);
-    return pick_pipe(sel) == 2 && pipe_fits(2, d) && d->cout == 32 && d->res.ptr &&
+    ConvPlan p = {};
+    return plan_pipe(p, sel_view(d, v), d) && p.pipe_cfg == 2 && !p.misfit && d->cout == 32 && d->res.ptr &&
            d->act == DBSR_ACT_NONE && d->post_act == DBSR_ACT_RELU;
 }
 
 extern "C" size_t dbsr_conv_workspace_bytes(const dbsr_conv_desc* d) {
-    if (!d || d->precise) return 0;
-    const int kf = kernel_for(d);
-    dbsr_conv_desc v;
-    const dbsr_conv_desc* sel = sel_view(d, v);
-    if (kf == 1) {
-        int wm, wn;
-        pick_tiled_tile(sel, wm, wn);
-        return splitk_bytes(make_convk(d), tiled_ksplit(sel, wm, wn));
-    }
-    if (kf != 0) return 0;
-    const ConvK ksel = make_convk(sel);
-    int m, n;
-    pick_generic_tile(ksel, m, n);
-    return splitk_bytes(make_convk(d), choose_ksplit(ksel, m, n));
+    return d ? conv_plan(d, SIZE_MAX).workspace : 0;
 }
 
 extern "C" int dbsr_set_conv_algo(int algo) {
@@ -3429,9 +3445,10 @@ extern "C" int dbsr_conv2d(const dbsr_conv_desc* d, void* stream) {
     // a partial cout tile at the last pixel of the last frame (where a run past ld would leave the allocation)
     if (d->res.ptr) DBSR_CHECK_ARG(d->res.c0 + d->cout <= d->res.ld, "conv2d: residual slice exceeds ld");
     if (d->gate.ptr) DBSR_CHECK_ARG(d->gate.c0 + d->cout <= d->gate.ld, "conv2d: gate slice exceeds ld");
+    const ConvPlan p = conv_plan(d, d->workspace_bytes);
     for (int w = 0; w < 3; ++w) {
         const dbsr_tensor& t = w == 0 ? d->y : w == 1 ? d->res : d->gate;
-        const int reach = conv_lane_reach(d, w);
+        const int reach = conv_lane_reach(d, p, w);
         DBSR_CHECK_ARG(reach < t.ld, "conv2d: a lane of the %s would address channel %d of a %d-channel pixel",
                        w == 0 ? "output" : w == 1 ? "residual" : "gate", reach, t.ld);
     }
@@ -3439,30 +3456,15 @@ extern "C" int dbsr_conv2d(const dbsr_conv_desc* d, void* stream) {
     DBSR_CHECK_ARG(npix < (1LL << 31), "conv2d: too many pixels");
 
     DBSR_CHECK_ARG(d->plan_h >= 0, "conv2d: plan_h must be >= 0");
+    if (p.precise16)
+        DBSR_CHECK_ARG(d->y.dtype == DBSR_F32 && d->cout <= 16, "conv2d: precise mode needs fp32 output, cout <= 16");
+    DBSR_CHECK_ARG(!p.misfit, "conv2d: a %d-row slab cannot take the tile chosen for plan_h = %d rows (use a multiple "
+                   "of 16)", d->out_h, d->plan_h);
     ConvK k = make_convk(d);
+    k.ksplit = p.ksplit;
     hipStream_t s = (hipStream_t)stream;
-    dbsr_conv_desc v;
-    const dbsr_conv_desc* sel = sel_view(d, v);
-    const long long npix_sel = (long long)sel->n_frames * sel->out_h * sel->out_w;
-    if (d->precise && d->x.dtype == DBSR_F16) {
-        DBSR_CHECK_ARG(d->y.dtype == DBSR_F32 && d->cout <= 16, "conv2d: precise mode needs fp32 output, cout <= 16");
-        k.ksplit = 1;
-        if (npix_sel >= 512 * 256) return launch_conv<float, 1, 4, f16_t>(k, s);
-        if (npix_sel >= 512 * 128) return launch_conv<float, 1, 2, f16_t>(k, s);
-        return launch_conv<float, 1, 1, f16_t>(k, s);
-    }
-    if (d->precise && d->x.dtype == DBSR_BF16) {
-        // bf16 activations, fp32-packed weights, fp32 MFMA: small fp32-output heads (the RGB predictor)
-        DBSR_CHECK_ARG(d->y.dtype == DBSR_F32 && d->cout <= 16, "conv2d: precise mode needs fp32 output, cout <= 16");
-        k.ksplit = 1;
-        if (npix_sel >= 512 * 256) return launch_conv<float, 1, 4, bf16_t>(k, s);
-        if (npix_sel >= 512 * 128) return launch_conv<float, 1, 2, bf16_t>(k, s);
-        return launch_conv<float, 1, 1, bf16_t>(k, s);
-    }
-    if (use_upsample(sel, k)) return d->x.dtype == DBSR_F16 ? launch_upsample<f16_t>(k, s) : launch_upsample<bf16_t>(k, s);
-    if (use_pointwise(sel)) return d->x.dtype == DBSR_F16 ? launch_pointwise<f16_t>(k, s) : launch_pointwise<bf16_t>(k, s);
-    if (d->x.dtype == DBSR_F16) return dispatch_conv<f16_t>(k, d, sel, s);
-    return d->x.dtype == DBSR_BF16 ? dispatch_conv<bf16_t>(k, d, sel, s) : dispatch_conv<float>(k, d, sel, s);
+    if (d->x.dtype == DBSR_F16) return launch_plan<f16_t>(p, k, d, s);
+    return d->x.dtype == DBSR_BF16 ? launch_plan<bf16_t>(p, k, d, s) : launch_plan<float>(p, k, d, s);
 }
 
 extern "C" int dbsr_resblock_ok(const dbsr_conv_desc* c1, const dbsr_conv_desc* c2) {
@@ -3476,7 +3478,7 @@ int resblock_launch(const dbsr_conv_desc* c1, const dbsr_conv_desc* c2, const fl
     DBSR_CHECK_ARG(c1->x.map.fpg > 0 && c2->y.map.fpg > 0 && c1->n_frames > 0, "resblock: bad frame map / sizes");
     const int C = resblock_channels(c1, c2);
     DBSR_CHECK_ARG(C, "resblock: needs two 16-bit 3x3/s1/p1 C -> C convs, C = 32 or 64 (conv1 ReLU; conv2 residual = "
-                   "conv1's input, post-ReLU), frames a multiple of 32 x 16 (C 32) / 16 x 16 (C 64), NHWC slices "
+                   "conv1's input, post-ReLU), frames a multiple of 32 x 16 (C 32) / 16 x 8 (C 64), NHWC slices "
                    "aligned to 8");
     DBSR_CHECK_ARG(!head_out || C == 32, "resblock_head: 32-channel ResBlocks only");
     const ConvK k1 = make_convk(c1);

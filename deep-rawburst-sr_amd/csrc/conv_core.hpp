@@ -16,7 +16,7 @@ inline int cin_pad(int cin) { return cin <= 16 ? round_up(cin, 8) : round_up(cin
 
 
 inline bool is16(int dtype) { return dtype == DBSR_BF16 || dtype == DBSR_F16; }   // 16-bit activations
-inline int esize(int dtype) { return is16(dtype) ? 2 : 4; }   // dbsr_set_conv_algo: 0 generic only, 1 LDS-tiled where applicable, 2 + pipelined
+inline int esize(int dtype) { return is16(dtype) ? 2 : 4; }
 
 
 struct ConvK {

@@ -35,6 +35,10 @@ import torch
 from . import _lib as L
 from ._lib import IDENTITY
 
+# the kernel family dbsr_conv2d runs a conv on, by dbsr_conv_kernel_for's answer (the profile's per-family rows)
+CONV_KERNEL_NAME = {L.CONV_GENERIC: 'conv2d_generic', L.CONV_TILED: 'conv3x3_tiled', L.CONV_PIPE: 'conv3x3_pipe',
+                    L.CONV_SHUFFLE: 'conv1x1_shuffle', L.CONV_WS: 'conv3x3_ws', L.CONV_POINTWISE: 'conv1x1',
+                    L.CONV_NARROW: 'conv3x3_narrow', L.CONV_KS128: 'conv3x3_ks128', L.CONV_SMALL: 'conv3x3_small'}
 BACKWARP_SCALE = {5: 0.625, 4: 1.25, 3: 2.5, 2: 5.0}      # fltBackwarp, pwcnet.py:121
 PWC_LEVEL_CH = {1: 16, 2: 32, 3: 64, 4: 96, 5: 128, 6: 196}
 DENSE_OUT = [128, 128, 96, 64, 32]                         # pwcnet.py:123-146
@@ -294,8 +298,7 @@ class Plan:
             self.kernel[len(self.ops) - 1] = 'conv3x3_pipe'
             return d
         self.add(name, L.lib().dbsr_conv2d, ctypes.byref(d), work=('flop', flop))
-        self.kernel[len(self.ops) - 1] = {4: 'conv3x3_ws', 7: 'conv3x3_ks128', 2: 'conv3x3_pipe', 1: 'conv3x3_tiled', 3: 'conv1x1_shuffle', 5: 'conv1x1', 6: 'conv3x3_narrow', 8: 'conv3x3_small'}.get(L.lib().dbsr_conv_kernel_for(d),
-                                                                                      'conv2d_generic')
+        self.kernel[len(self.ops) - 1] = CONV_KERNEL_NAME[L.lib().dbsr_conv_kernel_for(d)]
         return d
 
     def conv_fuse(self, name, pc, B, N, x, in_hw, ref, oth, fused, weights, xmap=IDENTITY, softmax=True):

@@ -112,9 +112,11 @@ def _packed(weight, bias, compute_dtype, shuffle, stream):
 
 
 def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, act=L.ACT_NONE, residual=None,
-           post_act=L.ACT_NONE, compute_dtype=torch.float32, out_f32=False, head=None, shuffle=1, max_blocks=0):
+           post_act=L.ACT_NONE, compute_dtype=torch.float32, out_f32=False, head=None, shuffle=1, max_blocks=0,
+           workspace=True):
     """act(conv2d(x) + bias) (+ residual, then post_act); NCHW in/out, computed by dbsr_conv2d.
     max_blocks > 0 caps the workgroups of a persistent kernel (dbsr_conv_desc.max_blocks).
+    workspace=False passes no split-K scratch (NULL, 0 bytes): a conv that would split K then runs unsplit.
     head = (w [hc, Cout, 1, 1], b [hc] | None): return ReLU(conv1x1(result, w, b)) as fp32 NCHW instead,
     computed by dbsr_conv2d_head (the conv's own result is not stored).
     shuffle = s > 1: return PixelShuffle(s) of the result (upsampling.py:51-66's conv + shuffle)."""
@@ -151,7 +153,7 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, act=L.ACT_NONE
     d.out_mode, d.shuffle = (L.OUT_SHUFFLE, shuffle) if shuffle > 1 else (L.OUT_NHWC, 0)
     need = L.lib().dbsr_conv_workspace_bytes(d)
     ws = torch.zeros(max(need // 4, 1), dtype=torch.float32, device=dev)
-    d.workspace, d.workspace_bytes = ws.data_ptr(), need
+    d.workspace, d.workspace_bytes = (ws.data_ptr(), need) if workspace else (None, 0)
     if head is not None:
         hw, hb = head
         hc = hw.shape[0]

@@ -161,10 +161,12 @@ int dbsr_set_conv_algo(int algo);
  * 6 narrow-output 3x3 (16-bit, cout <= 4, cin >= 256, pad 1: the PWC level-2 flow head), 7 cout-split
  * weight-stationary 128 -> 128 3x3 (ABI 21), 8 small-input 3x3 (16-bit, cin <= 8, cout a multiple of 16 up to 64,
  * no residual / gate: the encoder's and offset-feature extractor's first convs, ABI 21), 1 LDS-tiled, 0 generic. */
+enum { DBSR_CONV_GENERIC = 0, DBSR_CONV_TILED = 1, DBSR_CONV_PIPE = 2, DBSR_CONV_SHUFFLE = 3, DBSR_CONV_WS = 4,
+       DBSR_CONV_POINTWISE = 5, DBSR_CONV_NARROW = 6, DBSR_CONV_KS128 = 7, DBSR_CONV_SMALL = 8 };
 int dbsr_conv_kernel_for(const dbsr_conv_desc* d);
 /* The full dispatch decision for `d`: kernel_for * 1000000 + the variant (weight-stationary: tile width*100 +
  * height; pipelined: tile config; LDS-tiled: cout tile*1000 + pixel tile; generic: cout tile*10000 + pixel
- * tile*1000 + K split; precise: pixel tile).  Two descs with equal variants sum every output in the same
+ * tile*1000 + K split; precise over a 16-bit input: pixel tile).  Two descs with equal variants sum every output in the same
  * order (the frame-sharding tests compare a slab's variants with the whole image's). */
 int dbsr_conv_dispatch_variant(const dbsr_conv_desc* d);
 /* Host model of the highest channel of a pixel (c0 included) that any lane of the kernel dbsr_conv2d would

@@ -118,6 +118,34 @@ def test_conv2d_bf16(ops, case):
     np.testing.assert_allclose(out.numpy(), ref.numpy(), atol=1e-4, rtol=1e-4)
 
 
+# ((N, Cin, H, W, Cout), dbsr_conv_dispatch_variant): convs that split K -- the generic kernel's 1 x 1 tile in 19
+# slices (PWC level 6); the LDS-tiled kernel's 64-cout x 64-pixel tile in 4 slices
+SHORTFALL_CASES = [((104, 529, 1, 1, 32), 11019), ((1, 256, 16, 16, 64), 1464064)]
+
+
+@pytest.mark.parametrize('case,variant', SHORTFALL_CASES)
+def test_conv2d_workspace_shortfall(ops, case, variant):
+    """A conv that would split K, run with the workspace dbsr_conv_workspace_bytes asks for and with none (NULL, 0
+    bytes): dbsr_conv2d then runs it unsplit -- the generic kernel on the same tile, the LDS-tiled one on the tile
+    an unsplit conv takes (32 couts x 16 pixels here).  Both results match torch fp32 on the same bf16-rounded
+    operands to test_conv2d_bf16's tolerance, and they are not bitwise equal: the unsplit run sums each output in
+    one chain, the split one in slices."""
+    N, Cin, H, W, Cout = case
+    gen = torch.Generator().manual_seed(Cin * 1000 + Cout + 1)
+    x = torch.randn(N, Cin, H, W, generator=gen)
+    w = torch.randn(Cout, Cin, 3, 3, generator=gen) / (Cin * 9) ** 0.5
+    ref = F.conv2d(x.to(torch.bfloat16).float(), w.to(torch.bfloat16).float(), None, padding=1).numpy()
+    outs = []
+    for workspace in (True, False):
+        out = ops.conv2d(x.to(DEV), w.to(DEV), None, padding=1, compute_dtype=torch.bfloat16, out_f32=True,
+                         workspace=workspace).cpu().numpy()
+        assert ops.conv2d.last_variant == variant          # the plan with the workspace it asks for: a split
+        print('workspace %s: max abs err %.3g' % (workspace, np.abs(out - ref).max()))
+        np.testing.assert_allclose(out, ref, atol=1e-4, rtol=1e-4)
+        outs.append(out)
+    assert not np.array_equal(outs[0], outs[1])
+
+
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize('case', [(2, 64, 48, 48, 64), (2, 32, 70, 36, 32), (1, 128, 17, 33, 96)])
 def test_conv2d_tiled_vs_generic(ops, dtype, case):
