@@ -2003,33 +2003,27 @@ int launch_ks128(const ConvK& k, const dbsr_conv_desc* d, hipStream_t s) {
 //
 // Persistent blocks of 8 waves (2 per SIMD; one wave per SIMD with 4-group batches measured 87.5 against 62.7
 // us); every wave keeps both convs' weights in registers (A-fragments of the chunk-major pipe copy, 2 x 72
-// VGPRs) and runs 2 pixel groups per MFMA batch with its LDS reads two taps ahead.  Work unit = a 32x16 output tile.  Per tile: the input halo
+// VGPRs).  Work unit = a 32x16 output tile (geometry and schedule: rb32_sched.hpp).  Per tile: the input halo
 // (36 x 20 pixels) arrives by LDS-DMA one tile ahead into a double buffer (the halo_phys swizzle of the
 // weight-stationary kernel; out-of-frame pixels land zeros); conv1 runs on the 34 x 18 intermediate region
-// (39 flattened 16-pixel MFMA groups, 1.2x the output) and writes relu(conv1 + b1), rounded to T -- or zeros
-// outside the frame, conv2's padding -- into an LDS image laid out like the halo; one barrier; conv2 runs on
-// the 32 flattened groups of the tile, adds b2 and the residual (the halo's centre) and stores relu(...).
+// (1.2x the output) and writes relu(conv1 + b1), rounded to T -- or zeros outside the frame, conv2's padding --
+// into an LDS image laid out like the halo; one barrier; conv2 runs on the tile, adds b2 and the residual (the
+// halo's centre) and stores relu(...).
+// A wave is (column strip of 16, row band) in both convs and rolls its band's rows as ws_rows_body does: the
+// B-fragment of (image row i, kx) is read once (inline-asm ds_read_b128, AHEAD reads before use, a counted
+// lgkmcnt per read) and feeds rows i - ky with tap 3 ky + kx in both 16-cout blocks; a row's epilogue runs right
+// behind its last MFMAs, under those of the rows below.  conv1: bands of 5, 5, 4, 4 rows over the 32 main columns
+// (21 or 18 reads for 90 or 72 MFMAs), and the two edge columns as three flattened 16-pixel groups with per-lane
+// addresses, one each for three of the 4-row-band waves.  conv2: bands of 4 rows, 18 fragment reads for 72 MFMAs;
+// each row's residual is one more read of the same stream, and the row is stored as it finishes -- the stores
+// stay in flight over the next tile's first barrier (every DMA piece is older and drained at the second one).
 // Each output is the arithmetic of conv3x3_ws_kernel's epilogues 1 and 2 (taps in order from 0, bias after,
 // residual after the bias), so the result is bitwise that of the two dbsr_conv2d launches.
 // Block -> tiles: the 256 tiles of a round go to the blocks so that an XCD's 32 blocks take 32 consecutive
 // tiles (their halos overlap in that XCD's L2).
 // ------------------------------------------------------------------------------------------------
 namespace rbk {
-constexpr int TW = 32, TH = 16;
-constexpr int MW = TW + 2, MH = TH + 2, MPX = MW * MH;        // conv1 region 34 x 18
-constexpr int IW = TW + 4, IH = TH + 4, IPX = IW * IH;        // input halo 36 x 20
-constexpr int IN_PIECES = (IPX + 15) / 16;                    // 45 1-KiB pieces
-constexpr int IN_U4 = IN_PIECES * 64;
-constexpr int G1 = (MPX + 15) / 16;                           // 39 conv1 groups
-constexpr int MID_U4 = G1 * 16 * 4;
-constexpr int G2 = TW * TH / 16;                              // 32 conv2 groups
-constexpr int NW = 8;                                         // two waves per SIMD
-constexpr int PER = (IN_PIECES + NW - 1) / NW;                // 6 pieces per wave
-constexpr int Q1 = (G1 + NW - 1) / NW;                        // conv1 groups per wave (5; wave 7: 4)
-constexpr int Q2 = G2 / NW;                                   // conv2 groups per wave (4)
-constexpr int NG = 2;                                         // groups per MFMA batch
-constexpr int LDS_BYTES = (2 * IN_U4 + MID_U4) * 16 + 64 * 4;
-static_assert(LDS_BYTES <= 160 * 1024, "resblock LDS");
+using namespace rb32;
 }  // namespace rbk
 
 // HEAD: the decoder's RGB predictor (decoders.py:61, 1x1 32 -> head_cout + ReLU) on the block's fp32 output, as
@@ -2045,6 +2039,7 @@ __global__ __launch_bounds__(512, 1) void resblock32_kernel(ConvK k1, ConvK k2, 
     float* lbias = (float*)(lds + 2 * IN_U4 + MID_U4);            // [b1 (32)][b2 (32)]
     float* lhead = lbias + 64;                                    // HEAD: weights [4][32], bias [4]
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int strip = wave_strip(wave), band = wave_band(wave);
     const int H = k1.in_h, W = k1.in_w;
 
     // both convs' A-fragments: piece (half h, tap) of the chunk-major copy is lane-major 1 KiB
@@ -2081,6 +2076,7 @@ __global__ __launch_bounds__(512, 1) void resblock32_kernel(ConvK k1, ConvK k2, 
     const int pix_b = k1.x_ld * (int)sizeof(T);
     const unsigned frame_bytes = (unsigned)((long long)H * W * pix_b);
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) u32x4_t*)lds;
+    const unsigned lmid_b = lds0 + 2 * IN_U4 * 16;
     // the next tile's halo: inline-asm LDS-DMA (lds_dma16), so the compiler does not drain it before the conv1
     // epilogue's LDS writes; the drain is the vm_drain of the tile's second barrier
     auto dma = [&](const Tile& tl, int buf) {
@@ -2099,182 +2095,249 @@ __global__ __launch_bounds__(512, 1) void resblock32_kernel(ConvK k1, ConvK k2, 
         }
     };
 
-    // the 9 taps of NG 16-pixel groups (image rows iw wide, group j's tap-(0,0) pixel P0[j]): B-fragments read
-    // two taps ahead (a 3-deep ring per group)
-    // (NB = the batch's group count: NG, or the lone last group of conv1's odd count)
-    auto taps = [&](const u32x4_t* img, int iw, int g, const auto& P0, const Frag<T> (&w)[9][2], auto& acc) {
-        constexpr int NB = std::extent<std::remove_reference_t<decltype(P0)>>::value;
-        int bs[NB][8];
+    // B-fragment reads: byte address of pixel P0 + rho, k-group g (halo_phys), rho = pixel offset & 7, in the image at
+    // LDS byte address img; a read is then one base register and an immediate.  Formed at the head of each stream
+    // from the tile loop's opaque lane index: kept across the loop, the bases of three images took the registers
+    // of the accumulators
+    auto bases = [&](unsigned img, int P0, int g, unsigned (&ba)[8]) {
 #pragma unroll
-        for (int j = 0; j < NB; ++j)
+        for (int rho = 0; rho < 8; ++rho) ba[rho] = img + 16u * (4 * P0 + halo_phys(P0 + rho, g));
+    };
+    // relu(conv1 + b1) of this lane's 8 channels, rounded to T
+    auto mid_pack = [&](const f32x4_t& a0, const f32x4_t& a1, const float (&bv)[8]) {
+        u32x4_t o;
 #pragma unroll
-            for (int rho = 0; rho < 8; ++rho) bs[j][rho] = 4 * P0[j] + halo_phys(P0[j] + rho, g);
-        Frag<T> bq[NB][3];
-        auto rd = [&](int j, int tap) {
-            const int imm = (tap / 3) * iw + tap % 3;
-            Frag<T> b;
-            b.v = __builtin_bit_cast(bf16x8_t, img[bs[j][imm & 7] + 4 * imm]);
-            return b;
-        };
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            bq[j][0] = rd(j, 0);
-            bq[j][1] = rd(j, 1);
+        for (int e = 0; e < 2; ++e) {
+            o[e] = relu16x2(H16<T>::pack(a0[2 * e] + bv[2 * e], a0[2 * e + 1] + bv[2 * e + 1]));
+            o[2 + e] = relu16x2(H16<T>::pack(a1[2 * e] + bv[4 + 2 * e], a1[2 * e + 1] + bv[4 + 2 * e + 1]));
         }
-        StaticFor<0, 9>::run([&](auto t_) {
-            constexpr int tap = decltype(t_)::value;
-            const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                acc[j][0] = mma(w[tap][0], bq[j][tap % 3], tap == 0 ? z : acc[j][0]);
-                acc[j][1] = mma(w[tap][1], bq[j][tap % 3], tap == 0 ? z : acc[j][1]);
-                if constexpr (tap + 2 < 9) bq[j][(tap + 2) % 3] = rd(j, tap + 2);
-            }
-        });
-        // the scheduler's MFMA / DS-read interleave for small GEMM loops: without it the reads sank to their uses
-        // and every tap waited on its own read (measured: 69-71 us either way, two launches 75 us)
-        __builtin_amdgcn_iglp_opt(0);
+        return o;
     };
 
-    // a conv2 group's output: 8 channels of a pixel (16-bit NHWC), or with HEAD lane g's head channel (fp32 NCHW)
-    auto store_out = [&](const Tile& tl, int i, int g, int col, const u32x4_t& o) {
-        const int q = wave + NW * i;
-        const long long px = (long long)(q >> 1) * W + 16 * (q & 1) + col;
-        if constexpr (HEAD) {
-            if (g < k2.head_cout) ((float*)k2.y)[tl.y_off + px + (long long)g * H * W] = __uint_as_float(o[0]);
-        } else {
-            *(u32x4_t*)((T*)k2.y + tl.y_off + px * k2.y_ld + 8 * g) = o;
-        }
+    // ---- conv1, main columns: the band's NR intermediate rows from row R0, columns 16 strip .. + 15 ----
+    auto conv1_band = [&](auto nr_, int R0, unsigned lin_b, const Tile& tl, int g, int col, const float (&bv)[8]) {
+        constexpr int NR = decltype(nr_)::value;
+        using S = Rows<NR>;
+        const int c0 = 16 * strip + col;
+        unsigned ba[8];
+        bases(lin_b, R0 * IW + c0, g, ba);
+        const bool col_in = (unsigned)(tl.x0 - 1 + c0) < (unsigned)W;
+        f32x4_t acc[2][NR];
+        Frag<T> bq[AHEAD];
+        auto rd = [&](auto n_) {
+            constexpr int n = decltype(n_)::value, imm = rows_pix<NR>(n, IW);
+            // (asm operands name this lambda's own locals: clang does not capture for asm operands)
+            const unsigned a = ba[imm & 7];
+            bf16x8_t v;
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(a), "i"(64 * imm));
+            bq[n % AHEAD].v = v;
+        };
+        StaticFor<0, AHEAD>::run([&](auto n_) { rd(n_); });
+        StaticFor<0, S::READS>::run([&](auto n_) {
+            constexpr int n = decltype(n_)::value;
+            constexpr int newer = AHEAD - 1 < S::READS - 1 - n ? AHEAD - 1 : S::READS - 1 - n;
+            bf16x8_t v = bq[n % AHEAD].v;
+            asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "i"(newer));
+            Frag<T> bf;
+            bf.v = v;
+            StaticFor<0, 3>::run([&](auto ky_) {
+                constexpr int ky = decltype(ky_)::value;
+                if constexpr (S::feeds(n, ky)) {
+                    constexpr int r = S::read_row(n) - ky, tap = S::tap(n, ky);
+                    const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
+                    acc[0][r] = mma(w1[tap][0], bf, tap == 0 ? z : acc[0][r]);
+                    acc[1][r] = mma(w1[tap][1], bf, tap == 0 ? z : acc[1][r]);
+                }
+            });
+            if constexpr (n + AHEAD < S::READS) rd(std::integral_constant<int, n + AHEAD>{});
+            StaticFor<0, NR>::run([&](auto r_) {
+                constexpr int r = decltype(r_)::value;
+                if constexpr (n == S::row_done(r)) {
+                    const int p = (R0 + r) * MW + c0;
+                    const bool inside = col_in && (unsigned)(tl.y0 - 1 + R0 + r) < (unsigned)H;
+                    u32x4_t o = mid_pack(acc[0][r], acc[1][r], bv);
+                    if (!inside) o = u32x4_t{0u, 0u, 0u, 0u};
+                    lmid[4 * p + halo_phys(p, g)] = o;
+                }
+            });
+        });
     };
-    Tile cur = decode(0), prev = cur;
+    // ---- conv1, edge columns: flattened pixels 16 eg .. + 15 of the 36, one in-order 9-tap chain per lane ----
+    auto conv1_edge = [&](int eg, unsigned lin_b, const Tile& tl, int g, int col, const float (&bv)[8]) {
+        const int e = min(16 * eg + col, EDGE_PX - 1);
+        const int r = edge_row(e), c = edge_col(e);
+        unsigned ba[8];
+        bases(lin_b, r * IW + c, g, ba);
+        f32x4_t acc[2];
+        Frag<T> bq[AHEAD];
+        auto rd = [&](auto n_) {
+            constexpr int n = decltype(n_)::value, imm = edge_pix(n);
+            const unsigned a = ba[imm & 7];
+            bf16x8_t v;
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(a), "i"(64 * imm));
+            bq[n % AHEAD].v = v;
+        };
+        StaticFor<0, AHEAD>::run([&](auto n_) { rd(n_); });
+        StaticFor<0, EDGE_READS>::run([&](auto n_) {
+            constexpr int n = decltype(n_)::value;
+            constexpr int newer = AHEAD - 1 < EDGE_READS - 1 - n ? AHEAD - 1 : EDGE_READS - 1 - n;
+            bf16x8_t v = bq[n % AHEAD].v;
+            asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "i"(newer));
+            Frag<T> bf;
+            bf.v = v;
+            const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
+            acc[0] = mma(w1[n][0], bf, n == 0 ? z : acc[0]);
+            acc[1] = mma(w1[n][1], bf, n == 0 ? z : acc[1]);
+            if constexpr (n + AHEAD < EDGE_READS) rd(std::integral_constant<int, n + AHEAD>{});
+        });
+        const int p = r * MW + c;
+        const bool inside = (unsigned)(tl.y0 - 1 + r) < (unsigned)H && (unsigned)(tl.x0 - 1 + c) < (unsigned)W;
+        u32x4_t o = mid_pack(acc[0], acc[1], bv);
+        if (!inside) o = u32x4_t{0u, 0u, 0u, 0u};
+        if (16 * eg + col < EDGE_PX) lmid[4 * p + halo_phys(p, g)] = o;
+    };
+    // ---- conv2: the band's 4 output rows, columns 16 strip .. + 15; row y's epilogue (bias, residual, ReLU, or the
+    // head) consumes the stream's residual item and stores the row ----
+    auto conv2_band = [&](unsigned lin_b, const Tile& tl, int g, int col, const float (&bv)[8]) {
+        using S = Conv2;
+        constexpr int NR = S::NR;
+        const int c0 = 16 * strip + col, R0 = NR * band;
+        unsigned ba[8], br[8];
+        bases(lmid_b, R0 * MW + c0, g, ba);
+        bases(lin_b, (R0 + 2) * IW + c0 + 2, g, br);
+        const long long px0 = (long long)R0 * W + c0;
+        f32x4_t acc[2][NR];
+        Frag<T> bq[AHEAD];
+        auto rd = [&](auto n_) {
+            constexpr int n = decltype(n_)::value;
+            constexpr int imm = S::is_res(n) ? S::res_row(n) * IW : rows_pix<NR>(S::frag(n), MW);
+            const unsigned a = S::is_res(n) ? br[imm & 7] : ba[imm & 7];
+            bf16x8_t v;
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(a), "i"(64 * imm));
+            bq[n % AHEAD].v = v;
+        };
+        auto epilogue = [&](auto y_, const u32x4_t& rq) {
+            constexpr int y = decltype(y_)::value;
+            float v[8];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                v[r] = acc[0][y][r] + bv[r];
+                v[4 + r] = acc[1][y][r] + bv[4 + r];
+            }
+            const long long px = px0 + (long long)y * W;
+            if constexpr (HEAD) {
+                // the pipelined kernel's epilogue 4: fp32 ReLU(v + residual), partial head sums over this
+                // lane's 8 channels, reduced over the column's four g lanes; lane g keeps channel g
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[2 * e] = fmaxf(v[2 * e] + H16<T>::lo(rq[e]), 0.f);
+                    v[2 * e + 1] = fmaxf(v[2 * e + 1] + H16<T>::hi(rq[e]), 0.f);
+                }
+                float hs[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const float4 w0 = *(const float4*)(lhead + c * 32 + 8 * g);
+                    const float4 w4 = *(const float4*)(lhead + c * 32 + 8 * g + 4);
+                    float a = v[0] * w0.x;
+                    a = fmaf(v[1], w0.y, a); a = fmaf(v[2], w0.z, a); a = fmaf(v[3], w0.w, a);
+                    a = fmaf(v[4], w4.x, a); a = fmaf(v[5], w4.y, a); a = fmaf(v[6], w4.z, a);
+                    a = fmaf(v[7], w4.w, a);
+                    a += __shfl_xor(a, 16, 64);
+                    a += __shfl_xor(a, 32, 64);
+                    hs[c] = a;
+                }
+                const float hv = g == 0 ? hs[0] : g == 1 ? hs[1] : g == 2 ? hs[2] : hs[3];
+                if (g < k2.head_cout)
+                    ((float*)k2.y)[tl.y_off + px + (long long)g * H * W] = fmaxf(hv + lhead[128 + g], 0.f);
+            } else {
+                u32x4_t o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    o[e] = relu16x2(H16<T>::pack(v[2 * e] + H16<T>::lo(rq[e]), v[2 * e + 1] + H16<T>::hi(rq[e])));
+                *(u32x4_t*)((T*)k2.y + tl.y_off + px * k2.y_ld + 8 * g) = o;
+            }
+        };
+        StaticFor<0, AHEAD>::run([&](auto n_) { rd(n_); });
+        StaticFor<0, S::ITEMS>::run([&](auto n_) {
+            constexpr int n = decltype(n_)::value;
+            constexpr int newer = AHEAD - 1 < S::ITEMS - 1 - n ? AHEAD - 1 : S::ITEMS - 1 - n;
+            bf16x8_t v = bq[n % AHEAD].v;
+            asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "i"(newer));
+            if constexpr (S::is_res(n)) {
+                epilogue(std::integral_constant<int, S::res_row(n)>{}, __builtin_bit_cast(u32x4_t, v));
+            } else {
+                constexpr int f = S::frag(n);
+                Frag<T> bf;
+                bf.v = v;
+                StaticFor<0, 3>::run([&](auto ky_) {
+                    constexpr int ky = decltype(ky_)::value;
+                    if constexpr (Rows<NR>::feeds(f, ky)) {
+                        constexpr int r = Rows<NR>::read_row(f) - ky, tap = Rows<NR>::tap(f, ky);
+                        const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
+                        acc[0][r] = mma(w2[tap][0], bf, tap == 0 ? z : acc[0][r]);
+                        acc[1][r] = mma(w2[tap][1], bf, tap == 0 ? z : acc[1][r]);
+                    }
+                });
+            }
+            if constexpr (n + AHEAD < S::ITEMS) rd(std::integral_constant<int, n + AHEAD>{});
+        });
+    };
+    // this lane's 8 biases, in registers before the stream starts (first touched inside it, the compiler's wait for
+    // them would drain the stream's reads)
+    auto bias8 = [&](const float* b, int g, float (&bv)[8]) {
+        const float4 b0 = *(const float4*)(b + 8 * g), b1 = *(const float4*)(b + 8 * g + 4);
+        bv[0] = b0.x; bv[1] = b0.y; bv[2] = b0.z; bv[3] = b0.w;
+        bv[4] = b1.x; bv[5] = b1.y; bv[6] = b1.z; bv[7] = b1.w;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(bv[i]));
+    };
+
+    PIPE_STAMP(0);
+    Tile cur = decode(0);
     if (my_tiles > 0) dma(cur, 0);
-    u32x4_t outv[Q2];                   // the previous tile's conv2 outputs, stored after this tile's first barrier
+    vm_drain();                         // the first halo: from here on no DMA is in flight at a tile's first barrier
+    PIPE_STAMP(2);
     for (int ti = 0; ti < my_tiles; ++ti) {
-        dma_barrier();                  // B0: tile ti's halo landed; the intermediate image is free
+        PIPE_STAMP(3 + ti * 5);
+        // B0: tile ti's halo landed (drained at the previous tile's B1, or above); the intermediate image is free.
+        // Only the previous tile's stores can be in flight, and they may stay
+        DBSR_VM_WAIT(STORES);
+        __syncthreads();
+        PIPE_STAMP(4 + ti * 5);
         // lane-derived values recomputed per tile from an opaque copy of the lane index (hoisted out of the loop,
-        // the groups' per-lane LDS bases took registers for the whole loop)
+        // the per-lane LDS bases took registers for the whole loop)
         int ln = lane;
         asm volatile("" : "+v"(ln));
         const int g = ln >> 4, col = ln & 15;
-        if (ti > 0) {
-#pragma unroll
-            for (int i = 0; i < Q2; ++i) store_out(prev, i, g, col, outv[i]);
-        }
-        const u32x4_t* lin = lds + (ti & 1) * IN_U4;
+        const unsigned lin_b = lds0 + (ti & 1) * IN_U4 * 16;
         const bool more = ti + 1 < my_tiles;
         const Tile nxt = more ? decode(ti + 1) : cur;
         if (more) dma(nxt, (ti + 1) & 1);
-        // ---- conv1 on the intermediate region: groups wave + 8 i, in batches of NG and a lone last group (the odd
-        // fifth: batching it with a clamped duplicate cost a sixth of conv1's MFMAs and LDS reads) ----
         {
-            const float4 b0 = *(const float4*)(lbias + 8 * g), b1 = *(const float4*)(lbias + 8 * g + 4);
-            const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-            auto conv1 = [&](auto nb_, auto q0_) {
-                constexpr int NB = decltype(nb_)::value, Q0 = decltype(q0_)::value;
-                int pa[NB], P0[NB];
-#pragma unroll
-                for (int j = 0; j < NB; ++j) {
-                    pa[j] = min(16 * (wave + NW * (Q0 + j)) + col, MPX - 1);
-                    const int r = pa[j] / MW, c = pa[j] - r * MW;
-                    P0[j] = r * IW + c;
-                }
-                f32x4_t acc[NB][2];
-                taps(lin, IW, g, P0, w1, acc);
-#pragma unroll
-                for (int j = 0; j < NB; ++j) {
-                    const int p = 16 * (wave + NW * (Q0 + j)) + col;
-                    const int r = pa[j] / MW, c = pa[j] - r * MW;
-                    const int fy = cur.y0 - 1 + r, fx = cur.x0 - 1 + c;
-                    const bool inside = (unsigned)fy < (unsigned)H && (unsigned)fx < (unsigned)W;
-                    u32x4_t o;
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        o[e] = relu16x2(H16<T>::pack(acc[j][0][2 * e] + bv[2 * e], acc[j][0][2 * e + 1] + bv[2 * e + 1]));
-                        o[2 + e] = relu16x2(H16<T>::pack(acc[j][1][2 * e] + bv[4 + 2 * e],
-                                                         acc[j][1][2 * e + 1] + bv[4 + 2 * e + 1]));
-                    }
-                    if (!inside) o = u32x4_t{0u, 0u, 0u, 0u};
-                    if (p < MPX) lmid[4 * p + halo_phys(p, g)] = o;
-                }
-            };
-            StaticFor<0, Q1 / NG>::run([&](auto bt_) {
-                conv1(std::integral_constant<int, NG>{}, std::integral_constant<int, NG * decltype(bt_)::value>{});
-            });
-            if constexpr (Q1 % NG != 0) {
-                // wave-uniform: the waves whose last group lies inside the region (wave 7's fifth does not)
-                if (wave + NW * (Q1 - Q1 % NG) < G1)
-                    conv1(std::integral_constant<int, Q1 % NG>{}, std::integral_constant<int, Q1 - Q1 % NG>{});
+            float bv[8];
+            bias8(lbias, g, bv);
+            // wave-uniform: the 5-row bands, the 4-row bands, and the edge groups of three of the latter
+            if (c1_rows(band) == 5) {
+                conv1_band(std::integral_constant<int, 5>{}, c1_row0(band), lin_b, cur, g, col, bv);
+            } else {
+                conv1_band(std::integral_constant<int, 4>{}, c1_row0(band), lin_b, cur, g, col, bv);
+                if (edge_group(wave) >= 0) conv1_edge(edge_group(wave), lin_b, cur, g, col, bv);
             }
         }
+        PIPE_STAMP(5 + ti * 5);
         dma_barrier();                  // B1: the intermediate image is complete (the next halo's DMA, issued before
                                         // conv1, has landed too: no LDS-DMA crosses a barrier in flight)
-        // ---- conv2 on the tile: groups wave + 4 i, in batches of NG ----
+        PIPE_STAMP(6 + ti * 5);
         {
-            const float4 b0 = *(const float4*)(lbias + 32 + 8 * g), b1 = *(const float4*)(lbias + 32 + 8 * g + 4);
-            const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-            StaticFor<0, Q2 / NG>::run([&](auto bt_) {
-                constexpr int bt = decltype(bt_)::value;
-                int row[NG], cc[NG], P0[NG];
-#pragma unroll
-                for (int j = 0; j < NG; ++j) {
-                    const int q = wave + NW * (NG * bt + j);
-                    row[j] = q >> 1;
-                    cc[j] = 16 * (q & 1) + col;
-                    P0[j] = row[j] * MW + cc[j];
-                }
-                f32x4_t acc[NG][2];
-                taps(lmid, MW, g, P0, w2, acc);
-#pragma unroll
-                for (int j = 0; j < NG; ++j) {
-                    const int PR = (row[j] + 2) * IW + cc[j] + 2;
-                    const u32x4_t rq = lin[4 * PR + halo_phys(PR, g)];
-                    float v[8];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        v[r] = acc[j][0][r] + bv[r];
-                        v[4 + r] = acc[j][1][r] + bv[4 + r];
-                    }
-                    u32x4_t o;
-                    if constexpr (HEAD) {
-                        // the pipelined kernel's epilogue 4: fp32 ReLU(v + residual), partial head sums over this
-                        // lane's 8 channels, reduced over the column's four g lanes; lane g keeps channel g
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            v[2 * e] = fmaxf(v[2 * e] + H16<T>::lo(rq[e]), 0.f);
-                            v[2 * e + 1] = fmaxf(v[2 * e + 1] + H16<T>::hi(rq[e]), 0.f);
-                        }
-                        float hs[4];
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) {
-                            const float4 w0 = *(const float4*)(lhead + c * 32 + 8 * g);
-                            const float4 w1 = *(const float4*)(lhead + c * 32 + 8 * g + 4);
-                            float a = v[0] * w0.x;
-                            a = fmaf(v[1], w0.y, a); a = fmaf(v[2], w0.z, a); a = fmaf(v[3], w0.w, a);
-                            a = fmaf(v[4], w1.x, a); a = fmaf(v[5], w1.y, a); a = fmaf(v[6], w1.z, a);
-                            a = fmaf(v[7], w1.w, a);
-                            a += __shfl_xor(a, 16, 64);
-                            a += __shfl_xor(a, 32, 64);
-                            hs[c] = a;
-                        }
-                        const float hv = g == 0 ? hs[0] : g == 1 ? hs[1] : g == 2 ? hs[2] : hs[3];
-                        o = u32x4_t{__float_as_uint(fmaxf(hv + lhead[128 + g], 0.f)), 0u, 0u, 0u};
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            o[e] = relu16x2(H16<T>::pack(v[2 * e] + H16<T>::lo(rq[e]), v[2 * e + 1] + H16<T>::hi(rq[e])));
-                    }
-                    outv[NG * bt + j] = o;
-                }
-            });
+            float bv[8];
+            bias8(lbias + 32, g, bv);
+            conv2_band(lin_b, cur, g, col, bv);
         }
-        prev = cur;
+        PIPE_STAMP(7 + ti * 5);
         cur = nxt;
     }
-    if (my_tiles > 0) {
-#pragma unroll
-        for (int i = 0; i < Q2; ++i) store_out(prev, i, lane >> 4, lane & 15, outv[i]);
-    }
     vm_drain();                         // (no LDS-DMA outstanding at s_endpgm: tools/isa_audit.py)
+    PIPE_STAMP(1);
 }
 
 // byte range [lo, hi) that `n` frames of t cover: each stored image from its first used element (c0) to the last

@@ -4,6 +4,7 @@
 #include "common.hpp"
 #include "ks128_sched.hpp"
 #include "ws_sched.hpp"
+#include "rb32_sched.hpp"
 
 #include <vector>
 
